@@ -1,6 +1,11 @@
 """Benchmark: spectrogram frames/s of the VAE training step (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--prec bf16|fp32] [--config c3]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds
+the legs that take runs of their own (``extra``, ``cpu_baseline`` below).  ``--dump-outputs DIR``
+writes what the last timed step returned and left behind as ``DIR/<name>.npy`` (dump_outputs).
 
 Headline workload (``--config c3``, the default) = the metric's configuration: the full ML-VAE
 (VanillaVAE enc [80,64,64] z=32, BiLSTM 2x512 decoder with dropout 0.15, dec-FC
@@ -25,8 +30,10 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   kernels           secondary rooflines: the two big GEMMs against the bf16 MFMA peak, the fused
                     encoder (+reparameterisation + KL) and decoder-heads (+NLL) kernels against HBM
   cpu_baseline      the CPU oracle (oracle/vae_cpu.py, pinned to reference fixtures) timed on this
-                    host's cores on a bounded sample of the same model (rank 0, N=1)
+                    host's cores on a bounded sample of the same model (rank 0, N=1; --full only,
+                    null otherwise)
   extra (N=1 only)  c2 (configs[1], B=32, bf16) and the fp32 parity mode on the headline batch
+                    (--full only)
 """
 import argparse
 import json
@@ -337,6 +344,36 @@ def timed_run(eng, x, lens, steps, warmup, world, timers=None, norm=None):
     return dt, loss
 
 
+DUMP_MAX_ELEMS = {"params": 10_000_000, "grads": 4_000_000}   # 40 MB + 16 MB as float32
+
+
+def _dump_sample(t, max_elems, seed):
+    """The flat fp32 tensor on the host; above max_elems a fixed sample of it (seeded indices,
+    ascending, the same in every run of the same shape)."""
+    t = t.detach().reshape(-1).float().cpu()
+    if t.numel() > max_elems:
+        g = torch.Generator().manual_seed(seed)
+        idx = torch.randint(0, t.numel(), (max_elems,), generator=g).sort().values
+        t = t[idx]
+    return t.numpy()
+
+
+def dump_outputs(path, eng, loss):
+    """What a caller of the timed path holds after its last step, as <path>/<name>.npy (float32,
+    under 64 MB in all): `loss` = the returned [kld_loss, recon_loss, loss]; `params` = the
+    engine's flat parameters after that step's clip + Adam; `grads` = that step's flat gradient
+    (a fixed seeded sample of 4M entries where it is larger); `grad_norm` = its global norm."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {"loss": loss.detach().float().cpu().numpy(),
+              "grad_norm": eng.grad_norm.detach().float().cpu().numpy(),
+              "params": _dump_sample(eng.flat, DUMP_MAX_ELEMS["params"], 1),
+              "grads": _dump_sample(eng.grad, DUMP_MAX_ELEMS["grads"], 2)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def secondary(kern, B, T, cfg_name, dy_bytes=4, wg_fused=False):
     """Per-kernel rooflines of the timed secondary launches (HIP events, main stream); dy_bytes:
     the width of dY the engine's heads write (2 = bf16); wg_fused: the heads computed their small
@@ -483,8 +520,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--prec", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--config", default="c3", choices=list(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the N=1 c2 / fp32 extra runs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run also the legs that take runs of their own: the N=1 "
+                         "extra configurations / precisions and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0; dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the N=1 c2 / fp32 extra runs")
     ap.add_argument("--dry-run", action="store_true", help="process model only (gloo, no GPU)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend of the ranks (nccl = RCCL over xGMI; gloo: the "
@@ -534,6 +576,8 @@ def main():
     dyb = 2 if getattr(eng, "dy_bf16", False) else 4   # dY width the engine's bf16 step used
     zp = bool(getattr(eng, "zproj", False))             # layer 0's projection inside its forward
     wgf = bool(getattr(eng, "heads_wgrad", False))      # the heads' small weight gradients in-kernel
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, loss)
     del eng
     torch.cuda.empty_cache()
     if rank == 0:
@@ -583,9 +627,9 @@ def main():
             "kernels": secondary(kern, B, T, args.config, dyb, wgf) if args.prec == "bf16" else {},
             "kernel_ms": kern,
         }
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             out["extra"] = extra_runs(args, device)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.config)
         else:
             out["cpu_baseline"] = None

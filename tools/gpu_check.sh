@@ -3,4 +3,4 @@ cd $GRAFT_REPO_ROOT
 export PYTHONDONTWRITEBYTECODE=1
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > gpurun_out/pytest_gpu.log 2>&1 && \
 timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 && \
-timeout -k 10 180 python -u bench.py > gpurun_out/bench.log 2>&1
+timeout -k 10 180 python -u bench.py --full > "${LOG_DIR:-.}/bench.log" 2>&1
