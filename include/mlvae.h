@@ -237,6 +237,25 @@ int mlvae_boundary_bwd(size_t n, const float* za, const float* zb, const float* 
                        unsigned long long seed, unsigned long long offset, const float* dv,
                        const float* dbce, const float* dkld, float* dza, float* dzb, void* stream);
 
+/* MD-VAE pi path (csrc/pi.hip; ref:src/models/MD_VAE/model.py:119-150).  logits [n,2] fp32,
+ * contiguous and 8-byte aligned; n = B T frames; n == 0 is a no-op.
+ * mlvae_pi_sample: sampled_pi [n,2] = the one-hot row [1 - label, label] of
+ *   Categorical(logits = logits).  train != 0: label = (u >= p0), p0 = 1 / (1 + expf(l1 - l0)), u [n]
+ *   the U(0,1) draws (NULL: the 24-bit Philox(seed) draw of element offset + i) -- label 1 with
+ *   probability softmax(l)[1], exact at saturation (|l1 - l0| >= 160 never flips).  train == 0:
+ *   label = (l1 > l0), torch.argmax (a tie gives 0).
+ * mlvae_pi_nll_fwd: nll [n] = logsumexp(l0, l1) - l[label] = -Categorical.log_prob(label).  labels
+ *   [n] int32 are mlvae_viterbi_md's flvl_out; -1 (past T_i) counts as 0 (pad_sequence's zero
+ *   fill; the length mask removes those frames).  Any other label outside {0, 1} sets bit 32 of
+ *   *err (log_prob raises for it) and counts as 0.
+ * mlvae_pi_nll_bwd: dlogits [n,2], dlogits_k = dnll (softmax(l)_k - [k == label]). */
+int mlvae_pi_sample(size_t n, const float* logits, const float* u, unsigned long long seed,
+                    unsigned long long offset, int train, float* sampled_pi, void* stream);
+int mlvae_pi_nll_fwd(size_t n, const float* logits, const int* labels, float* nll, int* err,
+                     void* stream);
+int mlvae_pi_nll_bwd(size_t n, const float* logits, const int* labels, const float* dnll,
+                     float* dlogits, void* stream);
+
 /* MD-VAE Viterbi decode (csrc/decode.hip): decode_plvl_md_lbl_seqs_full
  * (ref:src/utils/decode_utils.py:374-565, run in the MD-VAE forward at ref:src/models/MD_VAE/
  * model.py:133-141).  logits [B,T,N] (phoneme recogniser output, row stride ldl), boundary_v

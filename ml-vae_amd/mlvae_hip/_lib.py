@@ -53,6 +53,9 @@ _SIGS = {
     "mlvae_conv1d_wgrad": [I, I, I, I, I, P, I, P, I, P, P, P, SZ, P],
     "mlvae_boundary_fwd": [SZ, P, P, P, P, U64, U64, P, P, P, P],
     "mlvae_boundary_bwd": [SZ, P, P, P, P, U64, U64, P, P, P, P, P, P],
+    "mlvae_pi_sample": [SZ, P, P, U64, U64, I, P, P],
+    "mlvae_pi_nll_fwd": [SZ, P, P, P, P, P],
+    "mlvae_pi_nll_bwd": [SZ, P, P, P, P, P],
     "mlvae_lstm1_fwd": [I, I, I, I, P, P, P, P, P, P, SZ, P, P],
     "mlvae_lstm1_bwd": [I, I, I, I, P, P, P, P, P, P, SZ, P, P],
     "mlvae_lstm_gates_fp16": [I, I, I],

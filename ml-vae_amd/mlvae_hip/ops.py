@@ -512,9 +512,9 @@ def _md_err():
 
 
 def _raise_md(err):
-    code = int(err.item())
+    code = int(err.item()) & 6  # bit 32 is the pi path's (raise_pi_err)
     if code:
-        err.zero_()
+        err.bitwise_and_(~6)
         raise AssertionError(
             "phoneme-recogniser targets: " +
             ("boundaries do not give one segment per phoneme from frame 0 " if code & 2 else "") +
@@ -591,6 +591,94 @@ class BoundaryHeadsFn(torch.autograd.Function):
 def boundary_heads(za, zb, boundary, u=None):
     seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if u is None else 0
     return BoundaryHeadsFn.apply(za, zb, boundary, u, seed)
+
+
+# --------------------------------------------------------------------------- MD-VAE pi path
+PI_ERR_LABEL = 32  # bit of the _md_err word: a decoded frame label outside {-1, 0, 1}
+
+
+def raise_pi_err():
+    """Read the device error word's pi bit (one host sync): ValueError as
+    Categorical.log_prob raises for a label outside its support."""
+    err = _md_err()
+    code = int(err.item())
+    if code & PI_ERR_LABEL:
+        err.bitwise_and_(~PI_ERR_LABEL)
+        raise ValueError("pi_nll: frame label outside {0, 1} (-1 = past the utterance's end) "
+                         "(ref:src/models/MD_VAE/model.py:149)")
+
+
+class PiSampleFn(torch.autograd.Function):
+    """sampled_pi of the MD-VAE forward (ref:src/models/MD_VAE/model.py:122-127): the one-hot
+    [1 - label, label] of a Categorical(logits) draw (train) or the argmax (eval).  u = the
+    U(0,1) draw per frame (None: Philox keyed by seed and frame index)."""
+
+    @staticmethod
+    def forward(ctx, logits, train, u, seed):
+        logits = _need(logits, "pi_logits")
+        if logits.shape[-1] != 2:
+            raise ValueError(f"pi_sample: pi_logits must end in 2 classes, got {tuple(logits.shape)}")
+        n = _rows(logits)
+        if u is not None:
+            u = _need(u, "uniforms")
+            if u.numel() != n:
+                raise ValueError(f"pi_sample: {u.numel()} uniforms for {n} frames")
+        out = torch.empty_like(logits)
+        check(lib().mlvae_pi_sample(n, _p(logits), _p(u) if u is not None else None, seed, 0,
+                                    1 if train else 0, _p(out), _stream()), "pi_sample")
+        ctx.mark_non_differentiable(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        return None, None, None, None
+
+
+def pi_sample(logits, train, u=None):
+    seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (train and u is None) else 0
+    return PiSampleFn.apply(logits, bool(train), u, seed)
+
+
+class PiNllFn(torch.autograd.Function):
+    """pi_nll_loss = -Categorical(logits).log_prob(labels) (ref:src/models/MD_VAE/model.py:145-149)
+    on the decode kernel's int32 frame labels [.., T] (-1 past T_i counts as 0)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels):
+        logits = _need(logits, "pi_logits")
+        if logits.shape[-1] != 2:
+            raise ValueError(f"pi_nll: pi_logits must end in 2 classes, got {tuple(logits.shape)}")
+        if not (labels.is_cuda and labels.dtype == torch.int32):
+            raise TypeError(f"pi_nll labels: expected an int32 HIP tensor, got {labels.dtype} on "
+                            f"{labels.device}")
+        labels = labels.contiguous()
+        n = _rows(logits)
+        if labels.numel() != n:
+            raise ValueError(f"pi_nll: {labels.numel()} labels for {n} frames")
+        nll = torch.empty(logits.shape[:-1], device=logits.device, dtype=torch.float32)
+        check(lib().mlvae_pi_nll_fwd(n, _p(logits), labels.data_ptr(), _p(nll), _p(_md_err()),
+                                     _stream()), "pi_nll_fwd")
+        ctx.save_for_backward(logits, labels)
+        ctx.mark_non_differentiable(labels)
+        return nll
+
+    @staticmethod
+    def backward(ctx, dnll):
+        logits, labels = ctx.saved_tensors
+        dnll = _need(dnll, "pi_nll grad")
+        dlogits = torch.empty_like(logits)
+        check(lib().mlvae_pi_nll_bwd(_rows(logits), _p(logits), labels.data_ptr(), _p(dnll),
+                                     _p(dlogits), _stream()), "pi_nll_bwd")
+        return dlogits, None
+
+
+def pi_nll(logits, labels, sync=True):
+    """sync=False leaves the error word unread (no host sync): the caller reads it with
+    raise_pi_err() where it syncs anyway (the MD-VAE recipe: at the stage's end)."""
+    nll = PiNllFn.apply(logits, labels)
+    if sync:
+        raise_pi_err()
+    return nll
 
 
 # --------------------------------------------------------------------------- GMM-VAE / H-VAE

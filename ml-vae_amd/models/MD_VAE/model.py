@@ -1,0 +1,222 @@
+"""The MD-VAE recipe (semantics of ref:src/models/MD_VAE/model.py:24-273).
+
+Three training targets in a cycle -- the phoneme recogniser (epochs 1, 4, ...), the boundary
+detector (2, 5, ...), the VAE (3, 6, ...) -- for TRAIN and for VALID; metrics, train_log lines
+and checkpoints (max_key plvl_md.F1) come from VALID under the VAE target and from TEST only.
+
+compute_forward, in the reference's order: normaliser; phoneme recogniser; boundary detector;
+for the VAE / TEST targets feat_fc + phn_recog_fc -> concat_fc -> rnn -> pi_fc -> pi_logits,
+sampled_pi (ops.pi_sample), the Viterbi MD decode, pi_nll_loss (ops.pi_nll on the decode's
+device labels), H-VAE encoder, decoder.  Modules whose losses the reference detaches (every
+upstream module outside its own target's epochs) run under torch.no_grad(): their parameters
+get no gradient (.grad stays None; the optimizer and the clip skip them).
+
+The decode stays on the device in TRAIN: its frame labels go to ops.pi_nll as the int32 tensor the
+kernel wrote, and its error word (with the pi path's) is read in on_stage_end, or earlier where
+the host lists are materialised (evaluation), raising the reference's AssertionError.
+
+``self.noise`` (tests): None, or a dict with any of boundary_u [10,B,T], pi_u [B,T], eps_v,
+eps_g, expo -- the draws injected into the modules instead of the library's Philox streams.
+"""
+import json
+import logging
+import warnings
+from enum import Enum, auto
+from pathlib import Path
+
+import torch
+
+from brain import Stage
+from mlvae_hip import ops
+from models.md_model import MDModel
+from utils.data_utils import apply_lens_to_loss, undo_padding
+from utils.decode_utils import decode_md_device, decoded_lists, raise_decode_err
+from utils.metric_stats.boundary_metric_stats import BoundaryMetricStats
+from utils.metric_stats.md_metric_stats import MDMetricStats
+
+logger = logging.getLogger(__name__)
+
+
+class Target(Enum):
+    PHN_RECOG = auto()
+    B_DETECTOR = auto()
+    VAE = auto()
+    TEST = auto()
+
+
+TRAIN_TARGETS = (Target.PHN_RECOG, Target.B_DETECTOR, Target.VAE)
+
+
+class SBModel(MDModel):
+    noise = None
+    _decode_err = None  # the stage's decode error words, OR-ed on the device
+
+    # ------------------------------------------------------------------ stages
+    def on_stage_start(self, stage, epoch=None):
+        super().on_stage_start(stage, epoch)
+        if stage in (Stage.TRAIN, Stage.VALID):
+            # VALID follows the epoch's training target (the reference's VALID -> TEST branch is
+            # unreachable: kept that way)
+            assert epoch is not None
+            self.target = TRAIN_TARGETS[(epoch - 1) % 3]
+        elif stage == Stage.TEST:
+            self.target = Target.TEST
+        else:
+            raise ValueError(f"invalid stage {stage}")
+        line = f"Epoch {epoch}, stage {stage.name}: target is {self.target.name}"
+        logger.info(line)
+        # train_log.txt gets lines from evaluated stages only: the schedule is recorded here
+        log = Path(getattr(self.hparams, "output_dir", "")) / "train_log.txt"
+        if stage != Stage.TEST and self.rank == 0 and log.is_file():
+            with open(log, "a") as f:
+                f.write(line + "\n")
+        self._decode_err = None
+        if self.to_run_evaluation(stage):  # the loss stats super() made, plus the MD metrics
+            self.stats_loggers["plvl_md_stats"] = MDMetricStats()
+            self.stats_loggers["boundary_stats"] = BoundaryMetricStats()
+        else:
+            self.stats_loggers = {}
+
+    def to_run_evaluation(self, stage):
+        return (stage == Stage.VALID and self.target == Target.VAE) or stage == Stage.TEST
+
+    def on_stage_end(self, stage, stage_loss, epoch=None):
+        self._raise_device_errors()
+        if self.to_run_evaluation(stage):
+            super().on_stage_end(stage, stage_loss, epoch)
+
+    def _raise_device_errors(self):
+        """The stage's device error words, read once (TRAIN reads none per batch)."""
+        err, self._decode_err = self._decode_err, None
+        if err is not None:
+            raise_decode_err(err.item())
+            ops.raise_pi_err()
+
+    # ------------------------------------------------------------------ forward
+    def compute_forward(self, batch, stage):
+        if not hasattr(self, "target"):
+            raise ValueError("target is not defined")
+        target = self.target
+        noise = self.noise or {}
+        batch = batch.to(self.device)
+        feats, feat_lens = batch["feat"]
+        predictions = {"losses": {}}
+        feats = self.hparams.normalizer(feats, feat_lens, epoch=self.hparams.epoch_counter.current)
+        feats = feats.contiguous()
+
+        def run(trained, fn):
+            """fn() with autograd when this epoch trains the module, else without (the
+            reference detaches its losses, and its output is only read detached)."""
+            if trained:
+                return fn()
+            with torch.no_grad():
+                return fn()
+
+        fa_boundary_seqs = batch["fa_boundary_seq"][0]
+        if target in (Target.PHN_RECOG, Target.VAE, Target.TEST):
+            seqs, seq_lens = batch["gt_cnncl_seq"]
+            phn = run(target == Target.PHN_RECOG, lambda: self.modules["phoneme_recognizer"](
+                feats, feat_lens, seqs, seq_lens, fa_boundary_seqs))
+            predictions["phn_recog_out"] = phn["out"]
+            predictions["losses"].update(phn["losses"])
+
+        if target in (Target.B_DETECTOR, Target.VAE, Target.TEST):
+            bnd = run(target == Target.B_DETECTOR, lambda: self.modules["boundary_detector"](
+                feats, feat_lens, fa_boundary_seqs, uniform_u=noise.get("boundary_u")))
+            predictions["boundary_v"] = bnd["boundary_v"]
+            predictions["losses"].update(bnd["losses"])
+
+        if target in (Target.VAE, Target.TEST):
+            feat_fc_out = self.modules["feat_fc"](feats)
+            phn_fc_out = self.modules["phn_recog_fc"](predictions["phn_recog_out"].detach())
+            rnn_in = self.modules["concat_fc"](torch.cat([feat_fc_out, phn_fc_out], dim=-1))
+            rnn_out = self.modules["rnn"](rnn_in)[0]          # (B, T, C)
+            pi_logits = self.modules["pi_fc"](rnn_out)        # (B, T, 2)
+            predictions["pi_logits"] = pi_logits
+            sampled_pi = ops.pi_sample(pi_logits, self.modules.training, u=noise.get("pi_u"))
+            predictions["sampled_pi"] = sampled_pi
+
+            # the Viterbi MD decode; its frame labels stay on the device for the NLL
+            seqs, seq_lens = batch["gt_cnncl_seq"]
+            decoded = decode_md_device(predictions, feat_lens, seqs, seq_lens,
+                                       prior=batch["prior"][0][0],
+                                       weight=getattr(self.hparams, "dec_weight", 1.0))
+            predictions["decoded_device"] = decoded
+            err = decoded[4]
+            self._decode_err = err if self._decode_err is None else self._decode_err | err
+            predictions["losses"]["pi_nll_loss"] = ops.pi_nll(pi_logits, decoded[1], sync=False)
+            if self.to_run_evaluation(stage):
+                self._decoded_lists(predictions)
+
+            enc = self.modules["encoder"](rnn_out, sampled_pi, eps_v=noise.get("eps_v"),
+                                          eps_g=noise.get("eps_g"), expo=noise.get("expo"))
+            predictions["losses"].update(enc["losses"])
+            dec = self.modules["decoder"](enc["sampled_h"], feats)
+            predictions["losses"].update(dec["losses"])
+        return predictions
+
+    def _decoded_lists(self, predictions):
+        """The batch's decode as the reference's host lists (one sync; raises its
+        AssertionError for a set error word), decoded once and kept in predictions."""
+        if "decoded_lists" not in predictions:
+            lists = decoded_lists(*predictions["decoded_device"])
+            ops.raise_pi_err()
+            predictions["decoded_lists"] = lists
+            predictions["decoded_boundary_seq"] = [torch.as_tensor(s) for s in lists[0]]
+            predictions["decoded_plvl_md_lbl_seq"] = [torch.tensor(s) for s in lists[2]]
+        return predictions["decoded_lists"]
+
+    # ------------------------------------------------------------------ objectives
+    def compute_objectives(self, predictions, batch, stage):
+        feats, feat_lens = batch["feat"]
+        losses = {key: apply_lens_to_loss(value, feat_lens)
+                  for key, value in predictions["losses"].items()}
+        loss = self.compute_and_save_losses(losses)
+
+        if self.to_run_evaluation(stage):
+            # the forward's decode read pi_logits, boundary_v and phn_recog_out as they are
+            # here: reused, not run again
+            boundary_seqs, _, plvl_md_lbl_seqs = self._decoded_lists(predictions)
+            gt_md_lbl_seqs = undo_padding(*batch["plvl_gt_md_lbl_seq"])
+            gt_boundary_seqs = undo_padding(*batch["gt_boundary_seq"])
+            self.stats_loggers["plvl_md_stats"].append(
+                ids=batch["id"], pred_md_lbl_seqs=plvl_md_lbl_seqs, gt_md_lbl_seqs=gt_md_lbl_seqs,
+                pred_boundary_seqs=boundary_seqs, gt_boundary_seqs=gt_boundary_seqs)
+            self.stats_loggers["boundary_stats"].append(
+                ids=batch["id"], predictions=boundary_seqs, targets=gt_boundary_seqs)
+
+        if stage == Stage.TEST:
+            self.save_md_result(batch, predictions)
+        return loss
+
+    # ------------------------------------------------------------------ results
+    def save_md_result(self, batch, predictions):
+        """datasets/<dataset_name>/saved_md_results/<model_name>.json: per utterance the
+        detected mispronunciations as [phoneme index, start, end], start / end relative to the
+        utterance's length (merged into the file's earlier entries)."""
+        self._decoded_lists(predictions)
+        results = {}
+        for i, utt_id in enumerate(batch["id"]):
+            boundary_seq = predictions["decoded_boundary_seq"][i]
+            md_lbl_seq = predictions["decoded_plvl_md_lbl_seq"][i]
+            n = len(boundary_seq)
+            edges = torch.cat([torch.where(boundary_seq == 1)[0], torch.tensor([n])]) / n
+            entries = []
+            for k in torch.where(md_lbl_seq == 1)[0]:
+                start, end = edges[k], edges[k + 1]
+                if start * n == end * n:
+                    warnings.warn(f"same start and end index: {int((start * n).item())}")
+                    assert False
+                entries.append([int(k.item()), start.item(), end.item()])
+            results[utt_id] = entries
+
+        save_dir = Path("datasets") / self.hparams.dataset_name / "saved_md_results"
+        save_dir.mkdir(parents=True, exist_ok=True)
+        save_path = save_dir / f"{self.hparams.model_name}.json"
+        if save_path.exists():
+            with open(save_path) as f:
+                merged = json.load(f)
+            merged.update(results)
+            results = merged
+        with open(save_path, "w") as f:
+            json.dump(results, f)

@@ -5,7 +5,10 @@
   reference's prepare_datasets, ref:src/utils/data_io.py:40-104).  The Kaldi / librosa feature
   computation that produces them is out of scope; when the files exist they are read as is.
 * ``SyntheticSet``: F-dim frames, lengths uniform in [min_frames, max_frames], values
-  log(1e-6 + |N(0,1)|^2) standardised (log-mel-like), seeded.
+  log(1e-6 + |N(0,1)|^2) standardised (log-mel-like), seeded.  ``md_labels=True``
+  (``synthetic.md_labels`` in config/run.yaml) adds the fields the MD-VAE recipe reads --
+  gt_cnncl_seq, fa_boundary_seq, gt_boundary_seq, plvl_gt_md_lbl_seq, prior -- drawn from a
+  generator of their own per utterance, so the features are the same with and without them.
 
 Batches follow SpeechBrain's PaddedBatch: batch['feat'] = (padded [B, Tmax, F], relative lengths
 [B]).  Under data parallelism rank r of W reads utterances [r*bs, (r+1)*bs) of every global batch
@@ -168,8 +171,46 @@ class PickledSet:
         return BatchLoader(self.items, batch_size, rank, world, stage, self.sorting)
 
 
+MIN_SEG = 5   # frames of the shortest synthetic phoneme segment
+JITTER = 2    # gt boundaries = forced-alignment boundaries moved by up to this many frames
+
+
+def _label_generator(seed, index):
+    """The label stream of one utterance (index -1: the set's prior): its own generator, so the
+    feature stream `g` of SyntheticSet draws exactly what it draws without labels."""
+    return torch.Generator().manual_seed((int(seed) * 1000003 + index + 1) % (2 ** 63 - 1) + 0x4D44)
+
+
+def _synthetic_md_labels(T, n_phonemes, g):
+    """The MD fields of one utterance of T frames (what phn_bce, the Viterbi decode and
+    boundary_md_scoring assert: a boundary at frame 0, one boundary per phoneme, ids in range):
+    L phonemes, L in [max(2, T // 12), max(2, T // 8)], each at least MIN_SEG frames long."""
+    lo, hi = max(2, T // 12), max(2, T // 8)
+    L = min(int(torch.randint(lo, hi + 1, (1,), generator=g)), max(T // MIN_SEG, 1))
+    # durations: MIN_SEG each, the remaining frames dealt out at random
+    extra = torch.randint(0, L, (max(T - MIN_SEG * L, 0),), generator=g)
+    dur = torch.bincount(extra, minlength=L) + min(MIN_SEG, T // L)
+    starts = torch.cumsum(dur, 0) - dur
+    fa = torch.zeros(T)
+    fa[starts] = 1.0
+    # interior boundaries move by at most JITTER < MIN_SEG / 2 frames: order and count are kept
+    move = torch.randint(-JITTER, JITTER + 1, (L,), generator=g)
+    move[0] = 0
+    if min(MIN_SEG, T // L) < MIN_SEG:
+        move.zero_()
+    gt = torch.zeros(T)
+    gt[starts + move] = 1.0
+    return {
+        "gt_cnncl_seq": torch.randint(0, n_phonemes, (L,), generator=g, dtype=torch.int64),
+        "fa_boundary_seq": fa,
+        "gt_boundary_seq": gt,
+        "plvl_gt_md_lbl_seq": (torch.rand(L, generator=g) < 0.2).to(torch.int64),
+    }
+
+
 class SyntheticSet:
-    def __init__(self, n_utts, feat_dim, min_frames, max_frames, seed, sorting="descending"):
+    def __init__(self, n_utts, feat_dim, min_frames, max_frames, seed, sorting="descending",
+                 md_labels=False, n_phonemes=39):
         g = torch.Generator().manual_seed(seed)
         lens = torch.randint(min_frames, max_frames + 1, (n_utts,), generator=g)
         self.items = []
@@ -177,6 +218,12 @@ class SyntheticSet:
             x = torch.log(1e-6 + torch.randn(L, feat_dim, generator=g) ** 2)
             x = (x - x.mean()) / x.std()
             self.items.append({"id": f"utt{i:05d}", "feat": x})
+        if md_labels:
+            # the decode's phoneme prior, in (0.05, 0.5): one per set, carried by every utterance
+            prior = 0.06 + 0.43 * torch.rand(n_phonemes + 2, generator=_label_generator(seed, -1))
+            for i, e in enumerate(self.items):
+                e.update(_synthetic_md_labels(e["feat"].shape[0], n_phonemes, _label_generator(seed, i)))
+                e["prior"] = prior.clone()
         _sort(self.items, sorting)
         self.sorting = sorting
 
@@ -208,5 +255,7 @@ def prepare_datasets(hparams):
     for j, split in enumerate(("train", "valid", "test")):
         sets.append(SyntheticSet(d.get(f"n_{split}", 32), F, d.get("min_frames", 50),
                                  d.get("max_frames", 200), hparams.get("seed", 123456) + j,
-                                 hparams.get("sorting", "descending")))
+                                 hparams.get("sorting", "descending"),
+                                 md_labels=bool(d.get("md_labels", False)),
+                                 n_phonemes=int(hparams.get("n_phonemes", 39))))
     return sets, None

@@ -20,6 +20,24 @@ def apply_lens_to_loss(loss, lens, reduction='mean'):
     return ops.masked_mean(loss, lens, reduction)
 
 
+def boundary_seq_to_seg_seq(boundary_seq):
+    """0/1 boundary flags [T] -> segments [L, 2] of (start, end) frame indices, one per flag
+    (ref:src/utils/data_utils.py:159-181).  The last segment's end is the NUMBER of boundaries,
+    not T, as in the reference (its T-terminated variant is commented out there): the MD
+    scores' IoU of the last phoneme is computed against that value, and stays comparable."""
+    idx = torch.where(boundary_seq == 1)[0]
+    segs = [[idx[i], idx[i + 1]] for i in range(len(idx) - 1)]
+    segs.append([idx[-1], len(idx)])
+    return torch.tensor(segs)
+
+
+def undo_padding(batch, lengths):
+    """Padded [B, Lmax] + relative lengths [B] -> list of per-utterance lists (SpeechBrain's
+    undo_padding: int(round(len * Lmax)) items each)."""
+    n = batch.shape[1]
+    return [batch[i, :int(torch.round(l * n))].tolist() for i, l in enumerate(lengths)]
+
+
 def apply_weight(x, weight):
     """Mixture weighting as one HIP launch (ref:src/utils/data_utils.py:32-64).
 
