@@ -1,5 +1,5 @@
-"""Same-process A/B of engine attributes (Python-side switches such as side_prep, zproj,
-split_overlap): one engine per config, the variants alternated for ROUNDS rounds of K timed steps.
+"""Same-process A/B of engine attributes (the Python-side tunables split_overlap, split_tail,
+force_overlap, bucket_allreduce): one engine per config, the variants alternated for ROUNDS rounds of K timed steps.
 usage: python tools/step_ab.py <config> "<attr=val,...>" "<attr=val,...>" ...   ("" = defaults)"""
 import os
 import statistics
