@@ -256,6 +256,35 @@ int mlvae_pi_nll_fwd(size_t n, const float* logits, const int* labels, float* nl
 int mlvae_pi_nll_bwd(size_t n, const float* logits, const int* labels, const float* dnll,
                      float* dlogits, void* stream);
 
+/* MD_VAE_sfl, the score-function (REINFORCE) estimator of the pi network (csrc/pi.hip;
+ * ref:src/models/MD_VAE_sfl/model.py:139-187).  K = pi_mcmc_num draws per frame; every [K,n,..]
+ * array is draw-major (draw k of frame i at index k n + i), fp32, contiguous.  n == 0 is a no-op.
+ * mlvae_pi_sample_k: sampled_pi [K,n,2], K one-hot draws per frame.  Draw k of frame i uses
+ *   u[k n + i] (u [K,n]; NULL: the Philox(seed) draw of element offset + k n + i): K = 1 is
+ *   mlvae_pi_sample bit for bit.  train == 0 is the argmax and requires K == 1 (status 1 otherwise).
+ * mlvae_sfl_fwd: with lp = log_softmax(logits[i]) and p = softmax(logits[i]),
+ *     reward[k,i]      = -(w_recon mean_F(recon[k,i,:]) + w_kld mean_Z(kld[k,i,:]) + w_nll pi_nll[i])
+ *     rif[i]           = (1/K) sum_k (reward[k,i] - baseline[i]) (-sum_c sampled_pi[k,i,c] lp_c)
+ *     baseline_loss[i] = (1/K) sum_k (baseline[i] - reward[k,i])^2
+ *     neg_entropy[i]   = sum_c p_c lp_c   (lp clamped to -FLT_MAX: exactly 0 at saturation)
+ *   recon [K,n,F], kld [K,n,Z], any F, Z >= 1 (float4 reads when F % 4 == Z % 4 == 0 and both are
+ *   16-byte aligned).  Fixed summation order, no atomics: a rerun is bit-identical.
+ * mlvae_sfl_bwd: d_rif, d_ent, d_bl [n] are the gradients of rif, neg_entropy, baseline_loss;
+ *     dlogits[i,c] = (d_rif/K) sum_k (reward[k,i] - baseline[i]) (p_c - sampled_pi[k,i,c])
+ *                    + d_ent p_c (lp_c - sum_j p_j lp_j)
+ *     dbaseline[i] = (2 d_bl/K) sum_k (baseline[i] - reward[k,i])
+ *   The reward and the baseline inside rif are constants (the reference detaches them): recon,
+ *   kld and pi_nll get no gradient. */
+int mlvae_pi_sample_k(size_t n, int K, const float* logits, const float* u, unsigned long long seed,
+                      unsigned long long offset, int train, float* sampled_pi, void* stream);
+int mlvae_sfl_fwd(size_t n, int K, int F, int Z, const float* logits, const float* sampled_pi,
+                  const float* recon, const float* kld, const float* pi_nll, const float* baseline,
+                  float w_recon, float w_kld, float w_nll, float* reward, float* rif,
+                  float* neg_entropy, float* baseline_loss, void* stream);
+int mlvae_sfl_bwd(size_t n, int K, const float* logits, const float* sampled_pi, const float* reward,
+                  const float* baseline, const float* d_rif, const float* d_ent, const float* d_bl,
+                  float* dlogits, float* dbaseline, void* stream);
+
 /* MD-VAE Viterbi decode (csrc/decode.hip): decode_plvl_md_lbl_seqs_full
  * (ref:src/utils/decode_utils.py:374-565, run in the MD-VAE forward at ref:src/models/MD_VAE/
  * model.py:133-141).  logits [B,T,N] (phoneme recogniser output, row stride ldl), boundary_v

@@ -56,6 +56,9 @@ _SIGS = {
     "mlvae_pi_sample": [SZ, P, P, U64, U64, I, P, P],
     "mlvae_pi_nll_fwd": [SZ, P, P, P, P, P],
     "mlvae_pi_nll_bwd": [SZ, P, P, P, P, P],
+    "mlvae_pi_sample_k": [SZ, I, P, P, U64, U64, I, P, P],
+    "mlvae_sfl_fwd": [SZ, I, I, I, P, P, P, P, P, P, F, F, F, P, P, P, P, P],
+    "mlvae_sfl_bwd": [SZ, I, P, P, P, P, P, P, P, P, P, P],
     "mlvae_lstm1_fwd": [I, I, I, I, P, P, P, P, P, P, SZ, P, P],
     "mlvae_lstm1_bwd": [I, I, I, I, P, P, P, P, P, P, SZ, P, P],
     "mlvae_lstm_gates_fp16": [I, I, I],

@@ -681,6 +681,94 @@ def pi_nll(logits, labels, sync=True):
     return nll
 
 
+# --------------------------------------------------------------------------- MD_VAE_sfl
+class PiSampleKFn(torch.autograd.Function):
+    """K Categorical(logits) draws per frame (ref:src/models/MD_VAE_sfl/model.py:147-152) as
+    one-hot rows [K, .., 2]; draw k of frame i uses uniform k n + i of u [K, ..] or of the
+    Philox stream.  Eval (train false) is the argmax: K must be 1."""
+
+    @staticmethod
+    def forward(ctx, logits, K, train, u, seed):
+        if K < 1 or (not train and K != 1):
+            raise ValueError(f"pi_sample_k: K must be >= 1 in train and 1 in eval (the argmax), got {K}")
+        if logits.shape[-1] != 2:
+            raise ValueError(f"pi_sample_k: pi_logits must end in 2 classes, got {tuple(logits.shape)}")
+        logits = _need(logits, "pi_logits")
+        n = _rows(logits)
+        if u is not None:
+            u = _need(u, "uniforms")
+            if u.numel() != K * n:
+                raise ValueError(f"pi_sample_k: {u.numel()} uniforms for {K} draws of {n} frames")
+        out = torch.empty((K,) + tuple(logits.shape), device=logits.device, dtype=torch.float32)
+        check(lib().mlvae_pi_sample_k(n, K, _p(logits), _p(u) if u is not None else None, seed, 0,
+                                      1 if train else 0, _p(out), _stream()), "pi_sample_k")
+        ctx.mark_non_differentiable(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        return None, None, None, None, None
+
+
+def pi_sample_k(logits, K, train, u=None):
+    seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (train and u is None) else 0
+    return PiSampleKFn.apply(logits, int(K), bool(train), u, seed)
+
+
+class SflLossesFn(torch.autograd.Function):
+    """The score-function terms of MD_VAE_sfl (ref:src/models/MD_VAE_sfl/model.py:170-186), the K
+    draws summed and divided by K: rif = (reward - baseline) * nll of the draw, the negative
+    entropy of Categorical(logits), and the baseline's squared error against the reward
+    -(w_recon mean(recon) + w_kld mean(kld) + w_nll pi_nll).  Gradients go to logits and baseline
+    only: the reference detaches the reward, and the baseline inside rif."""
+
+    @staticmethod
+    def forward(ctx, logits, sampled_pi, recon, kld, pi_nll, baseline, w_recon, w_kld, w_nll):
+        if logits.shape[-1] != 2:
+            raise ValueError(f"sfl_losses: pi_logits must end in 2 classes, got {tuple(logits.shape)}")
+        frames = tuple(logits.shape[:-1])
+        if sampled_pi.dim() != logits.dim() + 1 or tuple(sampled_pi.shape[1:]) != tuple(logits.shape):
+            raise ValueError(f"sfl_losses: sampled_pi must be [K, {', '.join(map(str, logits.shape))}], "
+                             f"got {tuple(sampled_pi.shape)}")
+        K = sampled_pi.shape[0]
+        if K < 1:
+            raise ValueError("sfl_losses: no draws (K = 0)")
+        for name, t in (("recon_loss", recon), ("vae_kld_loss", kld)):
+            if tuple(t.shape[:-1]) != (K,) + frames or t.shape[-1] < 1:
+                raise ValueError(f"sfl_losses: {name} must be [K, .., C] over {(K,) + frames}, "
+                                 f"got {tuple(t.shape)}")
+        for name, t in (("pi_nll_loss", pi_nll), ("baseline", baseline)):
+            if tuple(t.shape) != frames:
+                raise ValueError(f"sfl_losses: {name} must be {frames}, got {tuple(t.shape)}")
+        logits, sampled_pi = _need(logits, "pi_logits"), _need(sampled_pi, "sampled_pi")
+        recon, kld = _need(recon, "recon_loss"), _need(kld, "vae_kld_loss")
+        pi_nll, baseline = _need(pi_nll, "pi_nll_loss"), _need(baseline, "baseline")
+        n = _rows(logits)
+        reward = torch.empty((K,) + frames, device=logits.device, dtype=torch.float32)
+        rif, ent, bl = (torch.empty(frames, device=logits.device, dtype=torch.float32) for _ in range(3))
+        check(lib().mlvae_sfl_fwd(n, K, recon.shape[-1], kld.shape[-1], _p(logits), _p(sampled_pi),
+                                  _p(recon), _p(kld), _p(pi_nll), _p(baseline), float(w_recon),
+                                  float(w_kld), float(w_nll), _p(reward), _p(rif), _p(ent), _p(bl),
+                                  _stream()), "sfl_fwd")
+        ctx.save_for_backward(logits, sampled_pi, reward, baseline)
+        return rif, ent, bl
+
+    @staticmethod
+    def backward(ctx, d_rif, d_ent, d_bl):
+        logits, sampled_pi, reward, baseline = ctx.saved_tensors
+        d_rif, d_ent, d_bl = (_need(g, "sfl_losses grad") for g in (d_rif, d_ent, d_bl))
+        dlogits, dbaseline = torch.empty_like(logits), torch.empty_like(baseline)
+        check(lib().mlvae_sfl_bwd(_rows(logits), sampled_pi.shape[0], _p(logits), _p(sampled_pi),
+                                  _p(reward), _p(baseline), _p(d_rif), _p(d_ent), _p(d_bl),
+                                  _p(dlogits), _p(dbaseline), _stream()), "sfl_bwd")
+        return dlogits, None, None, None, None, dbaseline, None, None, None
+
+
+def sfl_losses(logits, sampled_pi, recon, kld, pi_nll, baseline, w_recon, w_kld, w_nll):
+    """(rif, neg_entropy, baseline_loss), each shaped like logits[..., 0]."""
+    return SflLossesFn.apply(logits, sampled_pi, recon, kld, pi_nll, baseline, w_recon, w_kld, w_nll)
+
+
 # --------------------------------------------------------------------------- GMM-VAE / H-VAE
 class GmmLatentFn(torch.autograd.Function):
     """GMM-VAE latent block on the stacked head output P = [pm | plv | m | lv | logits]

@@ -94,6 +94,23 @@ class SBModel(MDModel):
 
     # ------------------------------------------------------------------ forward
     def compute_forward(self, batch, stage):
+        predictions, batch, feats, feat_lens, noise = self._upstream(batch)
+        if self.target in (Target.VAE, Target.TEST):
+            rnn_out, pi_logits = self._pi_logits(predictions, feats, "phn_recog_fc")
+            sampled_pi = ops.pi_sample(pi_logits, self.modules.training, u=noise.get("pi_u"))
+            predictions["sampled_pi"] = sampled_pi
+            self._decode_and_nll(predictions, batch, feat_lens, stage)
+
+            enc = self.modules["encoder"](rnn_out, sampled_pi, eps_v=noise.get("eps_v"),
+                                          eps_g=noise.get("eps_g"), expo=noise.get("expo"))
+            predictions["losses"].update(enc["losses"])
+            dec = self.modules["decoder"](enc["sampled_h"], feats)
+            predictions["losses"].update(dec["losses"])
+        return predictions
+
+    def _upstream(self, batch):
+        """Normaliser, phoneme recogniser and boundary detector for the stage's target:
+        (predictions, batch on the device, feats, feat_lens, the injected noise)."""
         if not hasattr(self, "target"):
             raise ValueError("target is not defined")
         target = self.target
@@ -125,35 +142,31 @@ class SBModel(MDModel):
                 feats, feat_lens, fa_boundary_seqs, uniform_u=noise.get("boundary_u")))
             predictions["boundary_v"] = bnd["boundary_v"]
             predictions["losses"].update(bnd["losses"])
+        return predictions, batch, feats, feat_lens, noise
 
-        if target in (Target.VAE, Target.TEST):
-            feat_fc_out = self.modules["feat_fc"](feats)
-            phn_fc_out = self.modules["phn_recog_fc"](predictions["phn_recog_out"].detach())
-            rnn_in = self.modules["concat_fc"](torch.cat([feat_fc_out, phn_fc_out], dim=-1))
-            rnn_out = self.modules["rnn"](rnn_in)[0]          # (B, T, C)
-            pi_logits = self.modules["pi_fc"](rnn_out)        # (B, T, 2)
-            predictions["pi_logits"] = pi_logits
-            sampled_pi = ops.pi_sample(pi_logits, self.modules.training, u=noise.get("pi_u"))
-            predictions["sampled_pi"] = sampled_pi
+    def _pi_logits(self, predictions, feats, phn_fc):
+        """feat_fc + the recogniser output's FC (module name phn_fc) -> concat_fc -> rnn -> pi_fc:
+        (rnn_out (B, T, C), pi_logits (B, T, 2))."""
+        feat_fc_out = self.modules["feat_fc"](feats)
+        phn_fc_out = self.modules[phn_fc](predictions["phn_recog_out"].detach())
+        rnn_in = self.modules["concat_fc"](torch.cat([feat_fc_out, phn_fc_out], dim=-1))
+        rnn_out = self.modules["rnn"](rnn_in)[0]          # (B, T, C)
+        pi_logits = self.modules["pi_fc"](rnn_out)        # (B, T, 2)
+        predictions["pi_logits"] = pi_logits
+        return rnn_out, pi_logits
 
-            # the Viterbi MD decode; its frame labels stay on the device for the NLL
-            seqs, seq_lens = batch["gt_cnncl_seq"]
-            decoded = decode_md_device(predictions, feat_lens, seqs, seq_lens,
-                                       prior=batch["prior"][0][0],
-                                       weight=getattr(self.hparams, "dec_weight", 1.0))
-            predictions["decoded_device"] = decoded
-            err = decoded[4]
-            self._decode_err = err if self._decode_err is None else self._decode_err | err
-            predictions["losses"]["pi_nll_loss"] = ops.pi_nll(pi_logits, decoded[1], sync=False)
-            if self.to_run_evaluation(stage):
-                self._decoded_lists(predictions)
-
-            enc = self.modules["encoder"](rnn_out, sampled_pi, eps_v=noise.get("eps_v"),
-                                          eps_g=noise.get("eps_g"), expo=noise.get("expo"))
-            predictions["losses"].update(enc["losses"])
-            dec = self.modules["decoder"](enc["sampled_h"], feats)
-            predictions["losses"].update(dec["losses"])
-        return predictions
+    def _decode_and_nll(self, predictions, batch, feat_lens, stage):
+        """The Viterbi MD decode (its frame labels stay on the device) and pi_nll_loss on them."""
+        seqs, seq_lens = batch["gt_cnncl_seq"]
+        decoded = decode_md_device(predictions, feat_lens, seqs, seq_lens,
+                                   prior=batch["prior"][0][0],
+                                   weight=getattr(self.hparams, "dec_weight", 1.0))
+        predictions["decoded_device"] = decoded
+        err = decoded[4]
+        self._decode_err = err if self._decode_err is None else self._decode_err | err
+        predictions["losses"]["pi_nll_loss"] = ops.pi_nll(predictions["pi_logits"], decoded[1], sync=False)
+        if self.to_run_evaluation(stage):
+            self._decoded_lists(predictions)
 
     def _decoded_lists(self, predictions):
         """The batch's decode as the reference's host lists (one sync; raises its
