@@ -285,6 +285,39 @@ int mlvae_sfl_bwd(size_t n, int K, const float* logits, const float* sampled_pi,
                   const float* baseline, const float* d_rif, const float* d_ent, const float* d_bl,
                   float* dlogits, float* dbaseline, void* stream);
 
+/* The LSTM_FC baseline's frame-level MD head (csrc/flvl.hip; ref:src/models/LSTM_FC/model.py:29-67):
+ * the FCBlock's final Linear (two classes), the class-weighted BCE, the argmax and the MD counts,
+ * for N = B T frames.  All arrays fp32 and contiguous unless said otherwise; any E >= 1 (float4
+ * rows when E % 4 == 0 and h, w, dh are 16-byte aligned, scalar otherwise).  B, T < 0 or E < 1,
+ * a null pointer and a workspace that is too small give status 1; B == 0 or T == 0 (N == 0) is a
+ * no-op that returns 0.
+ * mlvae_flvl_head_fwd: h [N,E], w [2,E], bias [2], labels [B,T] (floats, 0 or 1), lens [B]
+ *   relative lengths (frame t of utterance b is valid iff (float)t < fp32(lens[b] T), as every
+ *   masked mean here).  With x = logits[i,:] = h[i,:] w^T + bias and y = [1 - label, label]:
+ *     loss_e[i,c] = pos_w_c y_c softplus(-x_c) + (1 - y_c) softplus(x_c)
+ *       = F.binary_cross_entropy_with_logits(x, y, reduction='none', pos_weight=[pos_w0, pos_w1]),
+ *       softplus(x) = max(x, 0) + log1pf(expf(-|x|)): finite at any logit; computed for padded
+ *       frames too (the masked mean drops them);
+ *     pred[b,t] int32 = (x_1 > x_0), torch.argmax (a tie gives 0); -1 past the utterance's length;
+ *     counts[b,:] int32 = over the valid frames of utterance b: both correct (pred 0, label 0),
+ *       both mispronounced (1, 1), missed (0, 1), false alarm (1, 0).  The entry zeroes counts
+ *       on the stream first; integer atomics, exact in any order.
+ *   A valid frame whose label is neither 0 nor 1 sets bit 64 of *err (it counts as 0); labels of
+ *   padded frames are not looked at.
+ * mlvae_flvl_head_bwd: logits [N,2] as the forward wrote them, dloss_e [N,2] the gradient of
+ *   loss_e.  dlogits[i,c] = dloss_e[i,c] ((1 - y_c) sigma(x_c) - pos_w_c y_c (1 - sigma(x_c)));
+ *   dh [N,E] = dlogits w, dw [2,E] = dlogits^T h, db [2] = sum_i dlogits[i,:].  dw and db are
+ *   per-workgroup partial sums in ws (mlvae_flvl_head_workspace_size bytes, at most
+ *   256 (2 E + 2) floats) added by a second kernel in workgroup order: no floating-point atomics,
+ *   a rerun is bit-identical. */
+size_t mlvae_flvl_head_workspace_size(int B, int T, int E);
+int mlvae_flvl_head_fwd(int B, int T, int E, const float* h, const float* w, const float* bias,
+                        const float* labels, const float* lens, float pos_w0, float pos_w1,
+                        float* logits, float* loss_e, int* pred, int* counts, int* err, void* stream);
+int mlvae_flvl_head_bwd(int B, int T, int E, const float* h, const float* w, const float* logits,
+                        const float* labels, const float* dloss_e, float pos_w0, float pos_w1,
+                        float* dh, float* dw, float* db, void* ws, size_t ws_bytes, void* stream);
+
 /* MD-VAE Viterbi decode (csrc/decode.hip): decode_plvl_md_lbl_seqs_full
  * (ref:src/utils/decode_utils.py:374-565, run in the MD-VAE forward at ref:src/models/MD_VAE/
  * model.py:133-141).  logits [B,T,N] (phoneme recogniser output, row stride ldl), boundary_v

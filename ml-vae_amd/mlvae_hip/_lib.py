@@ -59,6 +59,9 @@ _SIGS = {
     "mlvae_pi_sample_k": [SZ, I, P, P, U64, U64, I, P, P],
     "mlvae_sfl_fwd": [SZ, I, I, I, P, P, P, P, P, P, F, F, F, P, P, P, P, P],
     "mlvae_sfl_bwd": [SZ, I, P, P, P, P, P, P, P, P, P, P],
+    "mlvae_flvl_head_workspace_size": [I, I, I],
+    "mlvae_flvl_head_fwd": [I, I, I, P, P, P, P, P, F, F, P, P, P, P, P, P],
+    "mlvae_flvl_head_bwd": [I, I, I, P, P, P, P, P, F, F, P, P, P, P, SZ, P],
     "mlvae_lstm1_fwd": [I, I, I, I, P, P, P, P, P, P, SZ, P, P],
     "mlvae_lstm1_bwd": [I, I, I, I, P, P, P, P, P, P, SZ, P, P],
     "mlvae_lstm_gates_fp16": [I, I, I],
@@ -158,6 +161,7 @@ _RESTYPE = {
     "mlvae_viterbi_workspace_size": SZ,
     "mlvae_heads_bias_workspace_size": SZ,
     "mlvae_heads_wgrad_workspace_size": SZ,
+    "mlvae_flvl_head_workspace_size": SZ,
 }
 
 _lib = None

@@ -769,6 +769,87 @@ def sfl_losses(logits, sampled_pi, recon, kld, pi_nll, baseline, w_recon, w_kld,
     return SflLossesFn.apply(logits, sampled_pi, recon, kld, pi_nll, baseline, w_recon, w_kld, w_nll)
 
 
+# --------------------------------------------------------------------------- LSTM_FC frame-level head
+FLVL_ERR_LABEL = 64  # bit of the _md_err word: a valid frame's MD label is neither 0 nor 1
+
+
+def raise_flvl_err():
+    """Read the device error word's frame-label bit (one host sync): ValueError as
+    MDMetricStats raises for a non-binary label sequence."""
+    err = _md_err()
+    code = int(err.item())
+    if code & FLVL_ERR_LABEL:
+        err.bitwise_and_(~FLVL_ERR_LABEL)
+        raise ValueError("flvl_md_head: frame-level MD label outside {0, 1} in a valid frame "
+                         "(Only binary input values are supported)")
+
+
+class FlvlMdHeadFn(torch.autograd.Function):
+    """The LSTM_FC recipe after the FCBlock's last hidden layer (ref:src/models/LSTM_FC/
+    model.py:30-61): logits = h W^T + b, the class-weighted BCE-with-logits per frame and class
+    against [1 - label, label], the argmax (-1 past each length) and the per-utterance MD counts
+    (both correct, both mispronounced, missed, false alarm), one kernel; the backward is one
+    kernel and the fixed-order sum of its partials."""
+
+    @staticmethod
+    def forward(ctx, h, weight, bias, labels, lens, pw0, pw1):
+        if h.dim() != 3:
+            raise ValueError(f"flvl_md_head: h must be [B, T, E], got {tuple(h.shape)}")
+        B, T, E = h.shape
+        if E < 1:
+            raise ValueError("flvl_md_head: h has no features (E = 0)")
+        if tuple(weight.shape) != (2, E) or tuple(bias.shape) != (2,):
+            raise ValueError(f"flvl_md_head: weight must be [2, {E}] and bias [2], got "
+                             f"{tuple(weight.shape)} and {tuple(bias.shape)}")
+        if tuple(labels.shape) != (B, T):
+            raise ValueError(f"flvl_md_head: labels must be [{B}, {T}], got {tuple(labels.shape)}")
+        if tuple(lens.shape) != (B,):
+            raise ValueError(f"flvl_md_head: lens must be [{B}], got {tuple(lens.shape)}")
+        if labels.device != h.device:
+            raise TypeError(f"flvl_md_head labels: on {labels.device}, h on {h.device}")
+        h, weight, bias = _need(h, "flvl_md_head h"), _need(weight, "flvl_md_head weight"), \
+            _need(bias, "flvl_md_head bias")
+        labels = _need(labels.to(torch.float32), "flvl_md_head labels")
+        lens = _need(lens.to(h.device, torch.float32), "flvl_md_head lens")
+        logits = torch.empty(B, T, 2, device=h.device, dtype=torch.float32)
+        loss_e = torch.empty_like(logits)
+        pred = torch.empty(B, T, device=h.device, dtype=torch.int32)
+        counts = torch.empty(B, 4, device=h.device, dtype=torch.int32)
+        check(lib().mlvae_flvl_head_fwd(B, T, E, _p(h), _p(weight), _p(bias), _p(labels), _p(lens),
+                                        pw0, pw1, _p(logits), _p(loss_e), pred.data_ptr(),
+                                        counts.data_ptr(), _p(_md_err()), _stream()), "flvl_head_fwd")
+        ctx.save_for_backward(h, weight, logits, labels)
+        ctx.pw = (pw0, pw1)
+        ctx.mark_non_differentiable(logits, pred, counts)
+        return logits, loss_e, pred, counts
+
+    @staticmethod
+    def backward(ctx, dlogits, dloss_e, dpred, dcounts):
+        h, weight, logits, labels = ctx.saved_tensors
+        B, T, E = h.shape
+        dloss_e = _need(dloss_e, "flvl_md_head grad")
+        dh, dw = torch.empty_like(h), torch.empty_like(weight)
+        db = torch.empty(2, device=h.device, dtype=torch.float32)
+        if B * T == 0:
+            return dh, dw.zero_(), db.zero_(), None, None, None, None
+        l = lib()
+        ws = _workspace(l.mlvae_flvl_head_workspace_size(B, T, E), "flvl")
+        check(l.mlvae_flvl_head_bwd(B, T, E, _p(h), _p(weight), _p(logits), _p(labels), _p(dloss_e),
+                                    ctx.pw[0], ctx.pw[1], _p(dh), _p(dw), _p(db), _p(ws),
+                                    ws.numel() * 4, _stream()), "flvl_head_bwd")
+        return dh, dw, db, None, None, None, None
+
+
+def flvl_md_head(h, weight, bias, labels, lens, pos_weight):
+    """(logits [B,T,2], loss_e [B,T,2], pred int32 [B,T], counts int32 [B,4]) from h [B,T,E], the
+    final Linear's weight [2,E] and bias [2], the frame labels [B,T] (0 / 1) and the relative
+    lengths [B]; pos_weight = (class 0, class 1).  Gradients reach h, weight and bias through
+    loss_e only.  A label outside {0, 1} in a valid frame sets a bit of the device error word:
+    raise_flvl_err() reads it (where the counts are read, not per batch)."""
+    pw0, pw1 = (float(v) for v in pos_weight)
+    return FlvlMdHeadFn.apply(h, weight, bias, labels, lens, pw0, pw1)
+
+
 # --------------------------------------------------------------------------- GMM-VAE / H-VAE
 class GmmLatentFn(torch.autograd.Function):
     """GMM-VAE latent block on the stacked head output P = [pm | plv | m | lv | logits]

@@ -8,7 +8,8 @@
   log(1e-6 + |N(0,1)|^2) standardised (log-mel-like), seeded.  ``md_labels=True``
   (``synthetic.md_labels`` in config/run.yaml) adds the fields the MD-VAE recipe reads --
   gt_cnncl_seq, fa_boundary_seq, gt_boundary_seq, plvl_gt_md_lbl_seq, prior -- drawn from a
-  generator of their own per utterance, so the features are the same with and without them.
+  generator of their own per utterance, so the features are the same with and without them,
+  and flvl_gt_md_lbl_seq (the LSTM_FC baseline's frame-level targets), derived from them.
 
 Batches follow SpeechBrain's PaddedBatch: batch['feat'] = (padded [B, Tmax, F], relative lengths
 [B]).  Under data parallelism rank r of W reads utterances [r*bs, (r+1)*bs) of every global batch
@@ -200,11 +201,16 @@ def _synthetic_md_labels(T, n_phonemes, g):
         move.zero_()
     gt = torch.zeros(T)
     gt[starts + move] = 1.0
+    cnncl = torch.randint(0, n_phonemes, (L,), generator=g, dtype=torch.int64)
+    plvl = (torch.rand(L, generator=g) < 0.2).to(torch.int64)
+    # frame level: each phoneme's label over its gt_boundary_seq segment (no draw of its own)
+    flvl = plvl[torch.cumsum(gt, 0).to(torch.int64) - 1]
     return {
-        "gt_cnncl_seq": torch.randint(0, n_phonemes, (L,), generator=g, dtype=torch.int64),
+        "gt_cnncl_seq": cnncl,
         "fa_boundary_seq": fa,
         "gt_boundary_seq": gt,
-        "plvl_gt_md_lbl_seq": (torch.rand(L, generator=g) < 0.2).to(torch.int64),
+        "plvl_gt_md_lbl_seq": plvl,
+        "flvl_gt_md_lbl_seq": flvl,
     }
 
 

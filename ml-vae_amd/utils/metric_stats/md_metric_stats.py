@@ -29,7 +29,25 @@ class MDMetricStats(BaseMetricStats):
             for key in self.saved_seqs:
                 self.saved_seqs[key].extend(seqs[key])
 
+    def append_counts(self, ids, counts):
+        """The scores of a batch from its [B, 4] integer counts (both correct, both
+        mispronounced, missed, false alarm; ops.flvl_md_head's).  A device tensor is kept as it
+        is and read once by summarize(): no host sync per batch."""
+        if counts.dim() != 2 or counts.shape[1] != 4 or counts.shape[0] != len(ids):
+            raise ValueError(f"counts must be [{len(ids)}, 4], got {tuple(counts.shape)}")
+        self._pending.append((list(ids), counts.detach()))
+
+    def _flush_counts(self):
+        pending, self._pending = self._pending, []
+        for ids, counts in pending:
+            self._extend(ids, counts_md_scoring(counts.cpu()))
+
+    def clear(self):
+        super().clear()
+        self._pending = []
+
     def summarize(self, field=None):
+        self._flush_counts()
         means = super().summarize()
         # F1 of the corpus = F1 of the mean PRE and the mean REC, not the mean of the F1s
         pre, rec = means["PRE"], means["REC"]
@@ -71,6 +89,22 @@ def binary_seq_md_scoring(prediction, target):
     pre = hit / (hit + fa + EPS) * 100
     rec = hit / (hit + miss + EPS) * 100
     return {"ACC": acc, "PRE": pre, "REC": rec, "F1": 2 * pre * rec / (pre + rec + EPS)}
+
+
+def counts_md_scoring(counts):
+    """binary_seq_md_scoring from the four counts of each utterance ([B, 4] integers, in the order
+    of _counts): one score dict per utterance, in the same torch int32 / fp32 arithmetic, so
+    equal to the last bit to scoring the sequences themselves."""
+    counts = torch.as_tensor(counts).to("cpu", torch.int32)
+    if counts.dim() != 2 or counts.shape[1] != 4:
+        raise ValueError(f"counts must be [B, 4], got {tuple(counts.shape)}")
+    scores = []
+    for ok, hit, miss, fa in counts:
+        acc = (ok + hit) / (ok + hit + miss + fa + EPS) * 100
+        pre = hit / (hit + fa + EPS) * 100
+        rec = hit / (hit + miss + EPS) * 100
+        scores.append({"ACC": acc, "PRE": pre, "REC": rec, "F1": 2 * pre * rec / (pre + rec + EPS)})
+    return scores
 
 
 def compute_boundary_iou(pred_seg_seq, gt_seg_seq):
