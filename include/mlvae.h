@@ -334,6 +334,56 @@ int mlvae_viterbi_md(int B, int T, int N, int L, const float* logits, int ldl, c
                      size_t ws_bytes, int* boundary_out, int* flvl_out, int* plvl_out, int* lens_out,
                      int* err, void* stream);
 
+int mlvae_viterbi_md_ex(int B, int T, int N, int L, const float* logits, int ldl,
+                        const float* boundary_v, const float* pi_logits, const float* prior,
+                        const long long* seqs, const float* feat_lens, const float* seq_lens,
+                        float weight, int skip_empty, void* ws, size_t ws_bytes, int* boundary_out,
+                        int* flvl_out, int* plvl_out, int* lens_out, int* err, void* stream);
+
+/* Data-parallel shards of the MD recipes: the random streams over an utterance map.
+ * Every stream above is indexed over the utterances of the single-process batch.  A shard names
+ * the ones it holds with map = four values (utt_offset, seg_utts, seg_stride, total_utts), a host
+ * pointer, NULL = the identity: local utterance u of the shard's B is utterance
+ *     g(u) = (u / seg_utts) seg_stride + utt_offset + u % seg_utts
+ * of total_utts.  Rank r holding B_l of B_g utterances: (r B_l, B_l, B_l, B_g); MD_VAE_sfl's folded
+ * [K B_l, T, .] batch: (r B_l, B_l, B_g, K B_g).  With T frames per utterance the element counters
+ * are g T + t (frame streams), s total_utts T + g T + t (draw-major: the ten boundary draws, the K
+ * pi draws) and (g T + t) C + c (row-major [.., C]), so a shard draws bit for bit the slice of
+ * what the single process draws, and with the identity map each entry equals the one it extends
+ * (at offset 0).  Draws are per element: any C, any shard boundary.  Injected draws (u, expo) are
+ * the shard's own arrays, indexed locally.  seg_utts < 1, seg_stride < 1, utt_offset < 0 or
+ * total_utts < 1 give status 1; g(u) >= total_utts is allowed (the zero-length fillers of a short
+ * rank slice: their draws repeat counters of real utterances and are masked out by the lengths).
+ * B T C == 0 is a no-op.
+ * mlvae_randn_rows: out [B,T,C], the mlvae_randn stream.
+ * mlvae_dropout_rows: y = x * mask [B,T,C], the mlvae_dropout mask (the LSTM's inter-layer
+ *   dropout, rows 2H or H wide; the backward applies it to the gradient, y == x allowed).
+ * mlvae_pi_sample_rows: mlvae_pi_sample_k over logits [B,T,2], sampled_pi [K,B,T,2].
+ * mlvae_boundary_fwd_rows / _bwd_rows: mlvae_boundary_fwd / _bwd over [B,T], u [10,B,T].
+ * mlvae_gmm_latent_fwd_rows: mlvae_gmm_latent_fwd over rows = B T (B T <= INT_MAX); the backward
+ *   redraws nothing (it reads ysoft) and takes no map.
+ * mlvae_viterbi_md_ex (declared above): skip_empty != 0 makes a row with T_i == 0 and L_i == 0 --
+ *   the zero-length filler of a short rank slice -- write -1 everywhere and lens_out (0, 0)
+ *   without an error bit; every other empty or oversized row still sets bit 16.  skip_empty == 0
+ *   is mlvae_viterbi_md. */
+int mlvae_randn_rows(int B, int T, int C, unsigned long long seed, const long long* map, float* out,
+                     void* stream);
+int mlvae_dropout_rows(int B, int T, int C, const float* x, float* y, unsigned long long seed, float p,
+                       const long long* map, void* stream);
+int mlvae_pi_sample_rows(int B, int T, int K, const float* logits, const float* u,
+                         unsigned long long seed, const long long* map, int train, float* sampled_pi,
+                         void* stream);
+int mlvae_boundary_fwd_rows(int B, int T, const float* za, const float* zb, const float* y,
+                            const float* u, unsigned long long seed, const long long* map, float* v,
+                            float* bce, float* kld, void* stream);
+int mlvae_boundary_bwd_rows(int B, int T, const float* za, const float* zb, const float* y,
+                            const float* u, unsigned long long seed, const long long* map,
+                            const float* dv, const float* dbce, const float* dkld, float* dza,
+                            float* dzb, void* stream);
+int mlvae_gmm_latent_fwd_rows(int B, int T, int N, int Z, const float* P, int ldp, const float* eps,
+                              const float* expo, unsigned long long seed, const long long* map,
+                              float tau, float* z, float* kl, float* w, float* ysoft, void* stream);
+
 /* fp8 GEMM mode (BASELINE.json configs[4], csrc/gemm_fast.hip VAR 8 + csrc/fp8.hip): the decoder's
  * layer-1 input projection (ref:src/modules/decoder.py:14-15,22, nn.LSTM's x W_ih^T) on fp8 e4m3
  * (OCP) operands with per-tensor scales, v_mfma_scale_f32_16x16x128_f8f6f4, fp32 accumulate.

@@ -165,6 +165,51 @@ __device__ __forceinline__ void philox4(unsigned long long seed, unsigned long l
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
+// ---- the utterance map of a data-parallel shard ("The utterance map").
+// A random stream is indexed over the utterances of the single-process batch; a shard that holds
+// some of them finds each local utterance u at
+//     g(u) = (u / seg_utts) seg_stride + utt_offset + u % seg_utts
+// of total_utts.  Identity: (0, B, B, B).  Rank r's B_l of B_g utterances: (r B_l, B_l, B_l, B_g).
+// The K-folded [K B_l, T, .] batch of MD_VAE_sfl: (r B_l, B_l, B_g, K B_g).
+// Element counters over it (T frames per utterance):
+//     frame stream        g T + t
+//     draw-major stream   s total_utts T + g T + t
+//     row-major [.., C]   (g T + t) C + c
+struct UttMap {
+  unsigned long long off, seg, stride, total;
+};
+__device__ __forceinline__ unsigned long long utt_global(const UttMap& m, unsigned long long u) {
+  return (u / m.seg) * m.stride + m.off + u % m.seg;
+}
+// local frame index i = u T + t -> g(u) T + t
+__device__ __forceinline__ unsigned long long frame_global(const UttMap& m, unsigned long long i,
+                                                           unsigned T) {
+  const unsigned long long u = i / T;
+  return utt_global(m, u) * T + (i - u * T);
+}
+// Host: read the ABI's map (four values: utt_offset, seg_utts, seg_stride, total_utts; NULL = the
+// identity over B utterances).  g(u) >= total_utts is allowed: the zero-length fillers of a short
+// rank slice sit past the global batch's last utterance, their draws (counters a real utterance
+// also uses) are masked out by every length-aware consumer, and g only ever enters a counter.
+// For the same reason seg_stride < seg_utts passes: a folded slice with more rows than the global
+// batch has utterances (fillers again).
+static inline bool utt_map_load(const long long* map, int B, UttMap* m, const char* who) {
+  if (!map) {
+    m->off = 0; m->seg = m->stride = m->total = (unsigned long long)(B > 0 ? B : 1);
+    return true;
+  }
+  const long long off = map[0], seg = map[1], stride = map[2], total = map[3];
+  const bool ok = off >= 0 && seg >= 1 && stride >= 1 && total >= 1;
+  if (!ok) {
+    mlvae_set_error("%s: bad utterance map (utt_offset %lld, seg_utts %lld, seg_stride %lld, "
+                    "total_utts %lld) for %d utterances", who, off, seg, stride, total, B);
+    return false;
+  }
+  m->off = (unsigned long long)off; m->seg = (unsigned long long)seg;
+  m->stride = (unsigned long long)stride; m->total = (unsigned long long)total;
+  return true;
+}
+
 // Inter-layer LSTM dropout mask of flat element i (train mode, ref:src/modules/decoder.py:14):
 // keep iff u < 1-p, u = the 16-bit uniform in bits [16 (i & 3), +16) of
 //     r(q) = mix64(drop_key(seed) + q * 0x9E3779B97F4A7C15),  q = i >> 2

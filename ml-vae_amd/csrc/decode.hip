@@ -46,6 +46,7 @@ struct DecArgs {
   int* plvl_out;                   // [B, L] phoneme labels, -1 past L_i
   int* lens_out;                   // [B, 2] (T_i, L_i)
   int* err;
+  int skip_empty;                  // a row with T_i == 0 and L_i == 0 is a filler: no error bit
 };
 
 __global__ __launch_bounds__(DT) void viterbi_kernel(DecArgs a) {
@@ -64,6 +65,9 @@ __global__ __launch_bounds__(DT) void viterbi_kernel(DecArgs a) {
   }
   for (int l = tid; l < L; l += DT) a.plvl_out[(size_t)b * L + l] = -1;
   if (tid == 0) { a.lens_out[2 * b] = Ti; a.lens_out[2 * b + 1] = Li; }
+  // data parallel: the zero-length fillers of a short rank slice (utils/data_io.py) are rows, not
+  // utterances: -1 everywhere and lens (0, 0) as written above, and nothing to report
+  if (a.skip_empty && Ti == 0 && Li == 0) return;
   if (Ti <= 0 || Li <= 0 || Li > MAXL) {
     if (tid == 0) atomicOr(a.err, 16);
     return;  // the whole workgroup leaves before any barrier
@@ -184,11 +188,12 @@ __global__ __launch_bounds__(DT) void viterbi_kernel(DecArgs a) {
 
 extern "C" size_t mlvae_viterbi_workspace_size(int B, int T, int L) { return (size_t)B * T * L; }
 
-extern "C" int mlvae_viterbi_md(int B, int T, int N, int L, const float* logits, int ldl, const float* boundary_v,
-                                const float* pi_logits, const float* prior, const long long* seqs,
-                                const float* feat_lens, const float* seq_lens, float weight, void* ws,
-                                size_t ws_bytes, int* boundary_out, int* flvl_out, int* plvl_out,
-                                int* lens_out, int* err, void* stream) {
+extern "C" int mlvae_viterbi_md_ex(int B, int T, int N, int L, const float* logits, int ldl,
+                                   const float* boundary_v, const float* pi_logits, const float* prior,
+                                   const long long* seqs, const float* feat_lens, const float* seq_lens,
+                                   float weight, int skip_empty, void* ws, size_t ws_bytes,
+                                   int* boundary_out, int* flvl_out, int* plvl_out, int* lens_out,
+                                   int* err, void* stream) {
   if (B <= 0 || T <= 0) return 0;
   if (N <= 0 || L <= 0 || L > MAXL || ldl < N || !logits || !boundary_v || !pi_logits || !prior || !seqs ||
       !feat_lens || !seq_lens || !boundary_out || !flvl_out || !plvl_out || !lens_out || !err) {
@@ -203,8 +208,18 @@ extern "C" int mlvae_viterbi_md(int B, int T, int N, int L, const float* logits,
   a.T = T; a.N = N; a.L = L; a.logits = logits; a.ldl = ldl; a.bv = boundary_v; a.pil = pi_logits;
   a.prior = prior; a.seqs = seqs; a.feat_lens = feat_lens; a.seq_lens = seq_lens; a.weight = weight;
   a.path = static_cast<unsigned char*>(ws); a.bnd_out = boundary_out; a.flvl_out = flvl_out;
-  a.plvl_out = plvl_out; a.lens_out = lens_out; a.err = err;
+  a.plvl_out = plvl_out; a.lens_out = lens_out; a.err = err; a.skip_empty = skip_empty != 0;
   viterbi_kernel<<<B, DT, 0, (hipStream_t)stream>>>(a);
   MLVAE_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int mlvae_viterbi_md(int B, int T, int N, int L, const float* logits, int ldl, const float* boundary_v,
+                                const float* pi_logits, const float* prior, const long long* seqs,
+                                const float* feat_lens, const float* seq_lens, float weight, void* ws,
+                                size_t ws_bytes, int* boundary_out, int* flvl_out, int* plvl_out,
+                                int* lens_out, int* err, void* stream) {
+  return mlvae_viterbi_md_ex(B, T, N, L, logits, ldl, boundary_v, pi_logits, prior, seqs, feat_lens,
+                             seq_lens, weight, 0, ws, ws_bytes, boundary_out, flvl_out, plvl_out,
+                             lens_out, err, stream);
 }

@@ -218,6 +218,22 @@ __global__ __launch_bounds__(256) void randn_kernel(size_t n, unsigned long long
   }
 }
 
+// The same stream over the [B, T, C] rows of a data-parallel shard: element (b, t, c) draws the
+// counter (g(b) T + t) C + c (common.h UttMap), what the single process draws for it.  Per element:
+// any C.
+__global__ __launch_bounds__(256) void randn_rows_kernel(size_t n, unsigned T, unsigned C,
+                                                         unsigned long long seed, UttMap m,
+                                                         float* out) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const size_t row = i / C;
+    unsigned r[4];
+    philox4(seed, frame_global(m, row, T) * C + (i - row * C), r);
+    const float u1 = ((r[0] >> 8) + 1u) * (1.f / 16777217.f);  // (0, 1]
+    const float u2 = (r[1] >> 8) * (1.f / 16777216.f);
+    out[i] = sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
+  }
+}
+
 int grid_for(size_t total) {
   size_t g = (total + 255) / 256;
   if (g > 1024) g = 1024;
@@ -298,6 +314,21 @@ extern "C" int mlvae_randn(size_t n, unsigned long long seed, unsigned long long
   size_t g = (n + 255) / 256;
   if (g > 2048) g = 2048;
   randn_kernel<<<(int)g, 256, 0, (hipStream_t)stream>>>(n, seed, offset, out);
+  MLVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int mlvae_randn_rows(int B, int T, int C, unsigned long long seed, const long long* map,
+                                float* out, void* stream) {
+  if (B < 0 || T < 0 || C < 0) { mlvae_set_error("mlvae_randn_rows: B, T and C must be >= 0"); return 1; }
+  const size_t n = (size_t)B * T * C;
+  if (n == 0) return 0;
+  if (!out) { mlvae_set_error("mlvae_randn_rows: null pointer"); return 1; }
+  UttMap m;
+  if (!utt_map_load(map, B, &m, "mlvae_randn_rows")) return 1;
+  size_t g = (n + 255) / 256;
+  if (g > 2048) g = 2048;
+  randn_rows_kernel<<<(int)g, 256, 0, (hipStream_t)stream>>>(n, (unsigned)T, (unsigned)C, seed, m, out);
   MLVAE_CHECK_LAUNCH();
   return 0;
 }

@@ -32,6 +32,7 @@ struct GmmArgs {
   const float* dw;     // NULL = 0
   float* dP;           // [rows, lddp] same column layout as P
   int lddp;
+  UttMap m; unsigned T;  // MAP: rows = B T frames of a shard (common.h UttMap)
 };
 
 constexpr int GMM_MAX_N = 64;
@@ -44,6 +45,9 @@ __device__ __forceinline__ float exp1(unsigned long long seed, unsigned long lon
   return -logf(u);
 }
 
+// MAP: the Exp(1) draw of (row r, component n) is stream element (g T + t) N + n (common.h
+// UttMap), what the single process draws for that frame
+template <bool MAP>
 __global__ __launch_bounds__(256) void gmm_latent_fwd_kernel(GmmArgs a) {
   const int NZ = a.N * a.Z;
   const size_t total = (size_t)a.rows * NZ;
@@ -63,8 +67,9 @@ __global__ __launch_bounds__(256) void gmm_latent_fwd_kernel(GmmArgs a) {
     float u[GMM_MAX_N];
     float mx = -INFINITY;
     int arg = 0;
+    const unsigned long long gr = MAP ? frame_global(a.m, r, a.T) : r;
     for (int n = 0; n < a.N; ++n) {
-      const float e = a.expo ? a.expo[r * a.N + n] : exp1(a.seed, a.offset + r * a.N + n);
+      const float e = a.expo ? a.expo[r * a.N + n] : exp1(a.seed, a.offset + gr * a.N + n);
       u[n] = (lg[n] + -logf(e)) / a.tau;
       if (u[n] > mx) mx = u[n];
     }
@@ -177,7 +182,32 @@ extern "C" int mlvae_gmm_latent_fwd(int rows, int N, int Z, const float* P, int 
   GmmArgs a{};
   a.rows = rows; a.N = N; a.Z = Z; a.ldp = ldp; a.P = P; a.eps = eps; a.expo = expo;
   a.seed = seed; a.offset = offset; a.tau = tau; a.z = z; a.kl = kl; a.w = w; a.ysoft = ysoft;
-  gmm_latent_fwd_kernel<<<grid_of((size_t)rows * N * Z), 256, 0, (hipStream_t)stream>>>(a);
+  gmm_latent_fwd_kernel<false><<<grid_of((size_t)rows * N * Z), 256, 0, (hipStream_t)stream>>>(a);
+  MLVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+// The same over the rows = B T frames of a data-parallel shard: map = (utt_offset, seg_utts,
+// seg_stride, total_utts), NULL = the identity (then mlvae_gmm_latent_fwd at offset 0, bit for
+// bit).  The backward reads ysoft: it redraws nothing and needs no map.
+extern "C" int mlvae_gmm_latent_fwd_rows(int B, int T, int N, int Z, const float* P, int ldp,
+                                         const float* eps, const float* expo, unsigned long long seed,
+                                         const long long* map, float tau, float* z, float* kl,
+                                         float* w, float* ysoft, void* stream) {
+  if (B < 0 || T < 0 || (long long)B * T > 0x7fffffffll || N < 1 || N > GMM_MAX_N || Z < 1 ||
+      ldp < 4 * N * Z + N) {
+    mlvae_set_error("gmm_latent_fwd_rows: bad shape B=%d T=%d N=%d Z=%d ldp=%d", B, T, N, Z, ldp);
+    return 1;
+  }
+  if (!P || !eps || !z || !kl || !w || !ysoft) { mlvae_set_error("gmm_latent_fwd_rows: null pointer"); return 1; }
+  const int rows = B * T;
+  if (rows == 0) return 0;
+  GmmArgs a{};
+  if (!utt_map_load(map, B, &a.m, "gmm_latent_fwd_rows")) return 1;
+  a.T = (unsigned)T;
+  a.rows = rows; a.N = N; a.Z = Z; a.ldp = ldp; a.P = P; a.eps = eps; a.expo = expo;
+  a.seed = seed; a.offset = 0; a.tau = tau; a.z = z; a.kl = kl; a.w = w; a.ysoft = ysoft;
+  gmm_latent_fwd_kernel<true><<<grid_of((size_t)rows * N * Z), 256, 0, (hipStream_t)stream>>>(a);
   MLVAE_CHECK_LAUNCH();
   return 0;
 }

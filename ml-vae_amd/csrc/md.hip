@@ -124,11 +124,11 @@ __device__ double trigamma_d(double x) {
   return r + i + 0.5 * i2 + i * i2 * (1.0 / 6 - i2 * (1.0 / 30 - i2 * (1.0 / 42 - i2 / 30)));
 }
 
-// U(0,1) draw s of element i: injected (u[s*n + i]) or Philox(seed, offset + s*n + i), 24 bits
-__device__ __forceinline__ float draw(const float* u, unsigned long long seed, unsigned long long off,
+// U(0,1) draw s of local element i: injected (u[s*n + i]) or the 24-bit Philox(seed) draw of
+// stream element k (k = offset + s*n + i without an utterance map)
+__device__ __forceinline__ float draw(const float* u, unsigned long long seed, unsigned long long k,
                                       size_t n, int s, size_t i) {
   if (u) return u[(size_t)s * n + i];
-  const unsigned long long k = off + (unsigned long long)s * n + i;
   unsigned w[4];
   philox4(seed, k >> 2, w);
   return (w[k & 3] >> 8) * (1.f / 16777216.f);
@@ -141,11 +141,16 @@ struct BndArgs {
   float *v, *bce, *kld;                 // forward outputs (any may be NULL)
   const float *dv, *dbce, *dkld;        // backward cotangents (NULL = 0)
   float *dza, *dzb;                     // backward outputs
+  UttMap m; unsigned T;                 // MAP: the shard's utterance map (common.h), n = B T
 };
 
-template <bool BWD>
+// MAP: draw s of frame i is stream element s total_utts T + g T + t (common.h UttMap), what the
+// single process draws for that frame
+template <bool BWD, bool MAP>
 __global__ __launch_bounds__(256) void boundary_kernel(BndArgs g) {
+  const unsigned long long dstride = MAP ? g.m.total * g.T : g.n;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < g.n; i += (size_t)gridDim.x * 256) {
+    const unsigned long long k0 = g.off + (MAP ? frame_global(g.m, i, g.T) : i);
     const float za = g.za[i], zb = g.zb[i], y = g.y[i];
     const float a = softplus(za) + EPS_AB, b = softplus(zb) + EPS_AB;
     const double ad = a, bd = b, A0 = PRIOR_A, B0 = PRIOR_B;
@@ -158,7 +163,7 @@ __global__ __launch_bounds__(256) void boundary_kernel(BndArgs g) {
       }
       float vs = 0.f, bs = 0.f;
       for (int s = 0; s < NS; ++s) {
-        const float u = draw(g.u, g.seed, g.off, g.n, s, i) * 0.98f + 0.01f;
+        const float u = draw(g.u, g.seed, k0 + (unsigned long long)s * dstride, g.n, s, i) * 0.98f + 0.01f;
         float v = powf(1.f - powf(u, 1.f / b), 1.f / a);
         v = v * (1.f - 2.f * EPS_V) + EPS_V;
         vs += v;
@@ -177,7 +182,7 @@ __global__ __launch_bounds__(256) void boundary_kernel(BndArgs g) {
       const float gv = g.dv ? g.dv[i] / NS : 0.f, gb = g.dbce ? g.dbce[i] / NS : 0.f;
       if (gv != 0.f || gb != 0.f) {
         for (int s = 0; s < NS; ++s) {
-          const float u = draw(g.u, g.seed, g.off, g.n, s, i) * 0.98f + 0.01f;
+          const float u = draw(g.u, g.seed, k0 + (unsigned long long)s * dstride, g.n, s, i) * 0.98f + 0.01f;
           const float lu = logf(u);
           const float w = expf(lu / b);          // u^(1/b)
           const float sm = 1.f - w;
@@ -229,7 +234,7 @@ extern "C" int mlvae_boundary_fwd(size_t n, const float* za, const float* zb, co
   BndArgs g{};
   g.n = n; g.za = za; g.zb = zb; g.y = y; g.u = u; g.seed = seed; g.off = offset;
   g.v = v; g.bce = bce; g.kld = kld;
-  boundary_kernel<false><<<grid_n(n), 256, 0, (hipStream_t)stream>>>(g);
+  boundary_kernel<false, false><<<grid_n(n), 256, 0, (hipStream_t)stream>>>(g);
   MLVAE_CHECK_LAUNCH();
   return 0;
 }
@@ -243,7 +248,45 @@ extern "C" int mlvae_boundary_bwd(size_t n, const float* za, const float* zb, co
   BndArgs g{};
   g.n = n; g.za = za; g.zb = zb; g.y = y; g.u = u; g.seed = seed; g.off = offset;
   g.dv = dv; g.dbce = dbce; g.dkld = dkld; g.dza = dza; g.dzb = dzb;
-  boundary_kernel<true><<<grid_n(n), 256, 0, (hipStream_t)stream>>>(g);
+  boundary_kernel<true, false><<<grid_n(n), 256, 0, (hipStream_t)stream>>>(g);
+  MLVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+// The same over the [B, T] frames of a data-parallel shard: map = (utt_offset, seg_utts,
+// seg_stride, total_utts), NULL = the identity (then mlvae_boundary_fwd / _bwd at offset 0, bit
+// for bit).  u, when given, is the shard's own [10, B, T].
+extern "C" int mlvae_boundary_fwd_rows(int B, int T, const float* za, const float* zb, const float* y,
+                                       const float* u, unsigned long long seed, const long long* map,
+                                       float* v, float* bce, float* kld, void* stream) {
+  if (B < 0 || T < 0) { mlvae_set_error("mlvae_boundary_fwd_rows: B and T must be >= 0"); return 1; }
+  const size_t n = (size_t)B * T;
+  if (n == 0) return 0;
+  if (!za || !zb || !y) { mlvae_set_error("mlvae_boundary_fwd_rows: null input"); return 1; }
+  BndArgs g{};
+  if (!utt_map_load(map, B, &g.m, "mlvae_boundary_fwd_rows")) return 1;
+  g.T = (unsigned)T;
+  g.n = n; g.za = za; g.zb = zb; g.y = y; g.u = u; g.seed = seed; g.off = 0;
+  g.v = v; g.bce = bce; g.kld = kld;
+  boundary_kernel<false, true><<<grid_n(n), 256, 0, (hipStream_t)stream>>>(g);
+  MLVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int mlvae_boundary_bwd_rows(int B, int T, const float* za, const float* zb, const float* y,
+                                       const float* u, unsigned long long seed, const long long* map,
+                                       const float* dv, const float* dbce, const float* dkld,
+                                       float* dza, float* dzb, void* stream) {
+  if (B < 0 || T < 0) { mlvae_set_error("mlvae_boundary_bwd_rows: B and T must be >= 0"); return 1; }
+  const size_t n = (size_t)B * T;
+  if (n == 0) return 0;
+  if (!za || !zb || !y || !dza || !dzb) { mlvae_set_error("mlvae_boundary_bwd_rows: null pointer"); return 1; }
+  BndArgs g{};
+  if (!utt_map_load(map, B, &g.m, "mlvae_boundary_bwd_rows")) return 1;
+  g.T = (unsigned)T;
+  g.n = n; g.za = za; g.zb = zb; g.y = y; g.u = u; g.seed = seed; g.off = 0;
+  g.dv = dv; g.dbce = dbce; g.dkld = dkld; g.dza = dza; g.dzb = dzb;
+  boundary_kernel<true, true><<<grid_n(n), 256, 0, (hipStream_t)stream>>>(g);
   MLVAE_CHECK_LAUNCH();
   return 0;
 }

@@ -252,6 +252,22 @@ __global__ __launch_bounds__(256) void dropout_kernel(size_t n, const float* __r
   }
 }
 
+// The same mask over the [B, T, C] rows of a data-parallel shard: element (b, t, c) is mask
+// element (g(b) T + t) C + c (common.h UttMap).  Per element (its quad and lane from the global
+// index): a shard's rows need not start on a quad, any C.  In place (y == x) is fine.
+__global__ __launch_bounds__(256) void dropout_rows_kernel(size_t n, unsigned T, unsigned C,
+                                                           const float* __restrict__ x,
+                                                           float* __restrict__ y,
+                                                           unsigned long long seed, UttMap m, float p) {
+  const float keep = 1.f - p, scale = 1.f / keep;
+  const unsigned long long dk = drop_key(seed);
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const size_t row = i / C;
+    const unsigned long long e = frame_global(m, row, T) * C + (i - row * C);
+    y[i] = x[i] * drop_elem_scale(drop_quad(dk, e >> 2), (int)(e & 3), keep, scale);
+  }
+}
+
 int grid_for(size_t total, int cap) {
   size_t g = (total + 255) / 256;
   if (g > (size_t)cap) g = cap;
@@ -354,6 +370,22 @@ extern "C" int mlvae_dropout_ex(size_t n, const float* x, float* y, void* y_bf16
 extern "C" int mlvae_dropout(size_t n, const float* x, float* y, const float* mask,
                              unsigned long long seed, float p, void* stream) {
   return mlvae_dropout_ex(n, x, y, nullptr, mask, seed, 0ull, p, stream);
+}
+
+extern "C" int mlvae_dropout_rows(int B, int T, int C, const float* x, float* y,
+                                  unsigned long long seed, float p, const long long* map,
+                                  void* stream) {
+  if (B < 0 || T < 0 || C < 0) { mlvae_set_error("dropout_rows: B, T and C must be >= 0"); return 1; }
+  if (p < 0.f || p >= 1.f) { mlvae_set_error("dropout_rows: p=%f out of range", p); return 1; }
+  const size_t n = (size_t)B * T * C;
+  if (n == 0) return 0;
+  if (!x || !y) { mlvae_set_error("dropout_rows: null pointer"); return 1; }
+  UttMap m;
+  if (!utt_map_load(map, B, &m, "dropout_rows")) return 1;
+  dropout_rows_kernel<<<grid_for(n, 2048), 256, 0, (hipStream_t)stream>>>(
+      n, (unsigned)T, (unsigned)C, x, y, seed, m, p);
+  MLVAE_CHECK_LAUNCH();
+  return 0;
 }
 
 // ---- data parallel: the step's scalars ride in the gradient all-reduce.  hdr[4] is a float

@@ -23,11 +23,11 @@
 
 namespace {
 
-// U(0,1) draw of frame i: injected, or Philox(seed, offset + i), 24 bits (md.hip's draw)
-__device__ __forceinline__ float draw(const float* u, unsigned long long seed, unsigned long long off,
+// U(0,1) draw of local element i: injected (u[i]), or the 24-bit Philox(seed) draw of stream
+// element k (k = offset + i without an utterance map; md.hip's draw)
+__device__ __forceinline__ float draw(const float* u, unsigned long long seed, unsigned long long k,
                                       size_t i) {
   if (u) return u[i];
-  const unsigned long long k = off + i;
   unsigned w[4];
   philox4(seed, k >> 2, w);
   return (w[k & 3] >> 8) * (1.f / 16777216.f);
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void pi_sample_kernel(size_t n, const float2* 
       // p0 = softmax(l)[0]; saturates to exactly 0 (l1 - l0 large: expf = inf) or 1 (expf = 0),
       // and every draw is in [0, 1): u >= 0 always, u >= 1 never
       const float p0 = 1.f / (1.f + expf(l.y - l.x));
-      label = draw(u, seed, off, i) >= p0 ? 1 : 0;
+      label = draw(u, seed, off + i, i) >= p0 ? 1 : 0;
     } else {
       label = l.y > l.x ? 1 : 0;  // torch.argmax: the first maximum on a tie
     }
@@ -79,17 +79,23 @@ __global__ __launch_bounds__(256) void pi_nll_kernel(size_t n, const float2* __r
   if (!BWD && bad) atomicOr(err, bad);
 }
 
+// MAP: the frames are those of a shard (common.h UttMap, T frames per utterance): draw k of
+// frame i is stream element k total_utts T + g T + t, what the single process draws for it.
+template <bool MAP>
 __global__ __launch_bounds__(256) void pi_sample_k_kernel(size_t n, int K,
                                                           const float2* __restrict__ logits,
                                                           const float* __restrict__ u,
                                                           unsigned long long seed, unsigned long long off,
+                                                          UttMap m, unsigned T,
                                                           float2* __restrict__ sampled_pi) {
+  const unsigned long long dstride = MAP ? m.total * T : n;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
     const float2 l = logits[i];
     const float p0 = 1.f / (1.f + expf(l.y - l.x));  // as pi_sample_kernel
+    const unsigned long long gi = MAP ? frame_global(m, i, T) : i;
     for (int k = 0; k < K; ++k) {
       const size_t j = (size_t)k * n + i;
-      const int label = draw(u, seed, off, j) >= p0 ? 1 : 0;
+      const int label = draw(u, seed, off + (unsigned long long)k * dstride + gi, j) >= p0 ? 1 : 0;
       sampled_pi[j] = make_float2((float)(1 - label), (float)label);
     }
   }
@@ -251,8 +257,28 @@ extern "C" int mlvae_pi_sample_k(size_t n, int K, const float* logits, const flo
     if (K != 1) { mlvae_set_error("mlvae_pi_sample_k: eval (train == 0) is the argmax: K must be 1"); return 1; }
     return mlvae_pi_sample(n, logits, u, seed, offset, 0, sampled_pi, stream);
   }
-  pi_sample_k_kernel<<<grid_n(n), 256, 0, (hipStream_t)stream>>>(
-      n, K, (const float2*)logits, u, seed, offset, (float2*)sampled_pi);
+  pi_sample_k_kernel<false><<<grid_n(n), 256, 0, (hipStream_t)stream>>>(
+      n, K, (const float2*)logits, u, seed, offset, UttMap{}, 1u, (float2*)sampled_pi);
+  MLVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int mlvae_pi_sample_rows(int B, int T, int K, const float* logits, const float* u,
+                                    unsigned long long seed, const long long* map, int train,
+                                    float* sampled_pi, void* stream) {
+  if (B < 0 || T < 0) { mlvae_set_error("mlvae_pi_sample_rows: B and T must be >= 0"); return 1; }
+  const size_t n = (size_t)B * T;
+  if (n == 0) return 0;
+  if (!logits || !sampled_pi) { mlvae_set_error("mlvae_pi_sample_rows: null pointer"); return 1; }
+  if (K < 1) { mlvae_set_error("mlvae_pi_sample_rows: K must be >= 1"); return 1; }
+  UttMap m;
+  if (!utt_map_load(map, B, &m, "mlvae_pi_sample_rows")) return 1;
+  if (!train) {  // the argmax draws nothing: no map to apply
+    if (K != 1) { mlvae_set_error("mlvae_pi_sample_rows: eval (train == 0) is the argmax: K must be 1"); return 1; }
+    return mlvae_pi_sample(n, logits, u, seed, 0ull, 0, sampled_pi, stream);
+  }
+  pi_sample_k_kernel<true><<<grid_n(n), 256, 0, (hipStream_t)stream>>>(
+      n, K, (const float2*)logits, u, seed, 0ull, m, (unsigned)T, (float2*)sampled_pi);
   MLVAE_CHECK_LAUNCH();
   return 0;
 }

@@ -41,6 +41,14 @@ _SIGS = {
     "mlvae_lstm_bwd_ex": [I, I, I, I, P, P, P, P, P, P, P, SZ, P, P],
     "mlvae_viterbi_workspace_size": [I, I, I],
     "mlvae_viterbi_md": [I, I, I, I, P, I, P, P, P, P, P, P, F, P, SZ, P, P, P, P, P, P],
+    "mlvae_viterbi_md_ex": [I, I, I, I, P, I, P, P, P, P, P, P, F, I, P, SZ, P, P, P, P, P, P],
+    # the random streams over an utterance map (data-parallel shards; map: four long longs or None)
+    "mlvae_randn_rows": [I, I, I, U64, P, P, P],
+    "mlvae_dropout_rows": [I, I, I, P, P, U64, F, P, P],
+    "mlvae_pi_sample_rows": [I, I, I, P, P, U64, P, I, P, P],
+    "mlvae_boundary_fwd_rows": [I, I, P, P, P, P, U64, P, P, P, P, P],
+    "mlvae_boundary_bwd_rows": [I, I, P, P, P, P, U64, P, P, P, P, P, P, P],
+    "mlvae_gmm_latent_fwd_rows": [I, I, I, I, P, I, P, P, U64, P, F, P, P, P, P, P],
     "mlvae_phn_bce": [I, I, I, P, I, P, P, I, P, P, P, P, P, P, P],
     "mlvae_gemm_fp8": [I, I, I, P, I, P, I, P, I, P, P, P, I, P],
     "mlvae_fp8_scale_workspace_size": [],

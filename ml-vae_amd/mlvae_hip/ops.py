@@ -48,6 +48,73 @@ def _prec():
     return PREC[_state["prec"]]
 
 
+class shard:
+    """Context: the batch inside the block is a data-parallel shard of a global batch of
+    B_global utterances, its first utterance at utt_offset.  Every drawing op (randn, the LSTM's
+    inter-layer dropout, boundary_heads, pi_sample, pi_sample_k, GmmLatentFn) then draws, for
+    each of its utterances, bit for bit what the single process draws for that utterance of the
+    global batch (include/mlvae.h, "the random streams over an utterance map"): the ops take the
+    seeds from torch's CPU generator as they always do, so ranks seeded alike that make the same
+    calls in the same order agree.  Backward passes that recompute a draw (dropout, the boundary
+    draws) use the map of their forward.  global_lens = the relative lengths [B_global] of the
+    global batch: masked_mean's default global denominator inside the block.  folded(K) is the
+    context of MD_VAE_sfl's K-folded batch [K * B_local, T, .] (draw k of utterance b at row
+    k * B_local + b).  Without a context the ops call what they always called."""
+
+    def __init__(self, utt_offset, B_global, global_lens=None, K=1):
+        if utt_offset < 0 or B_global < 1 or K < 1:
+            raise ValueError(f"shard: utt_offset {utt_offset}, B_global {B_global}, K {K}")
+        self.utt_offset, self.B_global, self.K = int(utt_offset), int(B_global), int(K)
+        self.global_lens = global_lens
+
+    def folded(self, K):
+        return shard(self.utt_offset, self.B_global, self.global_lens, K)
+
+    def map(self, B):
+        """The ABI's (utt_offset, seg_utts, seg_stride, total_utts) for a batch of B rows."""
+        if B % self.K:
+            raise ValueError(f"shard: {B} rows are not {self.K} folds of a local batch")
+        Bl = max(B // self.K, 1)
+        # rows past B_global are the fillers of a short slice: masked out by their zero lengths
+        return (ctypes.c_longlong * 4)(self.utt_offset, Bl, self.B_global, self.K * self.B_global)
+
+    def global_frames(self, T):
+        """Valid frames of the global batch padded to T (the masked means' global count)."""
+        if self.global_lens is None:
+            return None
+        return valid_frames(self.global_lens, T)
+
+    def __enter__(self):
+        self.prev = _state.get("shard")
+        _state["shard"] = self
+        return self
+
+    def __exit__(self, *exc):
+        _state["shard"] = self.prev
+
+
+def current_shard():
+    return _state.get("shard")
+
+
+def valid_frames(lens, T):
+    """Frames the masked means count for relative lengths `lens` at padded length T: frame t is
+    valid iff (float)t < fp32(len * T) (csrc/common.h valid_frames), summed over the utterances."""
+    lim = torch.as_tensor(lens, dtype=torch.float32).cpu() * float(T)
+    c = torch.where(lim > 0, torch.ceil(lim).clamp(max=float(T)), torch.zeros_like(lim))
+    return int(c.sum().item())
+
+
+def _bt(shape, what):
+    """(B, T, C) of a [B, T, ...] batch: what the mapped streams index."""
+    if len(shape) < 2:
+        raise ValueError(f"{what}: a sharded draw needs a [B, T, ...] batch, got {tuple(shape)}")
+    C = 1
+    for d in shape[2:]:
+        C *= int(d)
+    return int(shape[0]), int(shape[1]), C
+
+
 def _stream():
     return torch.cuda.current_stream().cuda_stream
 
@@ -243,6 +310,11 @@ def randn(shape, generator=None):
     torch.manual_seed (ref:src/config/run.yaml:2-3) makes it reproducible."""
     seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator).item())
     out = torch.empty(*shape, device="cuda", dtype=torch.float32)
+    sh = current_shard()
+    if sh is not None:
+        B, T, C = _bt(out.shape, "randn")
+        check(lib().mlvae_randn_rows(B, T, C, seed, sh.map(B), _p(out), _stream()), "randn_rows")
+        return out
     check(lib().mlvae_randn(out.numel(), seed, 0, _p(out), _stream()), "randn")
     return out
 
@@ -321,10 +393,26 @@ class MaskedMeanFn(torch.autograd.Function):
         return dloss, None, None
 
 
-def masked_mean(loss, lens, reduction="mean"):
+def masked_mean(loss, lens, reduction="mean", global_frames=None):
+    """global_frames: the valid frames of the global batch this batch is a shard of (default
+    inside an ops.shard context that carries global_lens: its count).  The "mean" is then this
+    shard's share of the global mean -- local masked sum / (global_frames * C), so the shares
+    of all shards add up to the single-process mean -- and a shard of fillers alone gives 0."""
     if reduction not in RED:
         raise ValueError(f"unknown reduction {reduction}")
-    return MaskedMeanFn.apply(loss, lens, reduction)
+    sh = current_shard()
+    if global_frames is None and sh is not None and reduction == "mean" and loss.dim() >= 2:
+        global_frames = sh.global_frames(loss.shape[1])
+    if global_frames is None:
+        return MaskedMeanFn.apply(loss, lens, reduction)
+    if reduction != "mean":
+        raise ValueError("masked_mean: a global denominator belongs to reduction 'mean'")
+    B, T = loss.shape[0], loss.shape[1]
+    C = loss.numel() // (B * T) if B * T else 1
+    if global_frames < 1:
+        raise ValueError("masked_mean: the global batch has no valid frame")
+    # batchmean = masked sum / B (no local count in it): rescaled to sum / (global frames * C)
+    return MaskedMeanFn.apply(loss, lens, "batchmean") * (float(B) / (float(global_frames) * C))
 
 
 # --------------------------------------------------------------------------- BiLSTM
@@ -339,7 +427,12 @@ def _lstm_ws(B, H):
     return x, err
 
 
-def _dropout(src, dst, seed, p):
+def _dropout(src, dst, seed, p, sh=None):
+    if sh is not None:
+        B, T, C = _bt(src.shape, "lstm dropout")
+        check(lib().mlvae_dropout_rows(B, T, C, _p(src), _p(dst), seed, p, sh.map(B), _stream()),
+              "dropout_rows")
+        return
     check(lib().mlvae_dropout(src.numel(), _p(src), _p(dst), None, seed, p, _stream()), "dropout")
 
 
@@ -382,13 +475,14 @@ class LSTMFn(torch.autograd.Function):
             if li < L - 1 and dropout > 0:
                 s = (seed * 1000003 + li) & ((1 << 63) - 1)
                 hd = torch.empty_like(Y)
-                _dropout(Y, hd, s, dropout)
+                _dropout(Y, hd, s, dropout, current_shard())
                 seeds.append(s)
                 h = hd
             else:
                 seeds.append(None)
         ctx.save_for_backward(*inputs, *saved, *weights)
         ctx.H, ctx.L, ctx.ndir, ctx.dropout, ctx.seeds = H, L, ndir, dropout, seeds
+        ctx.shard = current_shard()  # the backward recomputes the masks under the forward's map
         # nn.LSTM's (h_n, c_n) [L*ndir, B, H]: every layer's state after its last step (t = T-1
         # forward, t = 0 reverse; no packing, as nn.LSTM on a padded batch)
         hn = torch.empty(L * ndir, B, H, device=x.device, dtype=torch.float32)
@@ -456,7 +550,7 @@ class LSTMFn(torch.autograd.Function):
                 base = nw * li + 4 * d
                 dW[base:base + 4] = [gwi, gwh, gbi, gbh]
             if li > 0 and ctx.seeds[li - 1] is not None:
-                _dropout(dx, dx, ctx.seeds[li - 1], ctx.dropout)
+                _dropout(dx, dx, ctx.seeds[li - 1], ctx.dropout, ctx.shard)
             dy = dx
         if int(err.item()) != 0:
             raise RuntimeError("LSTM recurrence hand-off timed out")
@@ -569,10 +663,16 @@ class BoundaryHeadsFn(torch.autograd.Function):
         y = _need(y.to(za.device, torch.float32), "boundary_seqs")
         u = _need(u, "uniforms") if u is not None else None
         v, bce, kld = torch.empty_like(za), torch.empty_like(za), torch.empty_like(za)
-        check(lib().mlvae_boundary_fwd(za.numel(), _p(za), _p(zb), _p(y), _p(u) if u is not None else None,
-                                       seed, 0, _p(v), _p(bce), _p(kld), _stream()), "boundary_fwd")
+        sh = current_shard() if u is None else None  # injected draws are the shard's own
+        if sh is not None:
+            B, T, _ = _bt(za.shape, "boundary_heads")
+            check(lib().mlvae_boundary_fwd_rows(B, T, _p(za), _p(zb), _p(y), None, seed, sh.map(B),
+                                                _p(v), _p(bce), _p(kld), _stream()), "boundary_fwd_rows")
+        else:
+            check(lib().mlvae_boundary_fwd(za.numel(), _p(za), _p(zb), _p(y), _p(u) if u is not None else None,
+                                           seed, 0, _p(v), _p(bce), _p(kld), _stream()), "boundary_fwd")
         ctx.save_for_backward(za, zb, y, *([u] if u is not None else []))
-        ctx.seed, ctx.has_u = seed, u is not None
+        ctx.seed, ctx.has_u, ctx.shard = seed, u is not None, sh
         return v, bce, kld
 
     @staticmethod
@@ -582,9 +682,15 @@ class BoundaryHeadsFn(torch.autograd.Function):
         u = t[3] if ctx.has_u else None
         grads = [None if g is None else _need(g, "grad") for g in (dv, dbce, dkld)]
         dza, dzb = torch.empty_like(za), torch.empty_like(zb)
+        gp = [(_p(g) if g is not None else None) for g in grads]
+        if ctx.shard is not None:
+            B, T, _ = _bt(za.shape, "boundary_heads")
+            check(lib().mlvae_boundary_bwd_rows(B, T, _p(za), _p(zb), _p(y), None, ctx.seed,
+                                                ctx.shard.map(B), *gp, _p(dza), _p(dzb), _stream()),
+                  "boundary_bwd_rows")
+            return dza, dzb, None, None, None
         check(lib().mlvae_boundary_bwd(za.numel(), _p(za), _p(zb), _p(y), _p(u) if u is not None else None,
-                                       ctx.seed, 0, *[(_p(g) if g is not None else None) for g in grads],
-                                       _p(dza), _p(dzb), _stream()), "boundary_bwd")
+                                       ctx.seed, 0, *gp, _p(dza), _p(dzb), _stream()), "boundary_bwd")
         return dza, dzb, None, None, None
 
 
@@ -624,6 +730,13 @@ class PiSampleFn(torch.autograd.Function):
             if u.numel() != n:
                 raise ValueError(f"pi_sample: {u.numel()} uniforms for {n} frames")
         out = torch.empty_like(logits)
+        sh = current_shard() if (train and u is None) else None
+        if sh is not None:
+            B, T, _ = _bt(logits.shape, "pi_sample")
+            check(lib().mlvae_pi_sample_rows(B, T, 1, _p(logits), None, seed, sh.map(B), 1, _p(out),
+                                             _stream()), "pi_sample_rows")
+            ctx.mark_non_differentiable(out)
+            return out
         check(lib().mlvae_pi_sample(n, _p(logits), _p(u) if u is not None else None, seed, 0,
                                     1 if train else 0, _p(out), _stream()), "pi_sample")
         ctx.mark_non_differentiable(out)
@@ -700,6 +813,13 @@ class PiSampleKFn(torch.autograd.Function):
             if u.numel() != K * n:
                 raise ValueError(f"pi_sample_k: {u.numel()} uniforms for {K} draws of {n} frames")
         out = torch.empty((K,) + tuple(logits.shape), device=logits.device, dtype=torch.float32)
+        sh = current_shard() if (train and u is None) else None
+        if sh is not None:
+            B, T, _ = _bt(logits.shape, "pi_sample_k")
+            check(lib().mlvae_pi_sample_rows(B, T, K, _p(logits), None, seed, sh.map(B), 1, _p(out),
+                                             _stream()), "pi_sample_rows")
+            ctx.mark_non_differentiable(out)
+            return out
         check(lib().mlvae_pi_sample_k(n, K, _p(logits), _p(u) if u is not None else None, seed, 0,
                                       1 if train else 0, _p(out), _stream()), "pi_sample_k")
         ctx.mark_non_differentiable(out)
@@ -865,6 +985,15 @@ class GmmLatentFn(torch.autograd.Function):
         kl = torch.empty_like(z)
         w = torch.empty(*P.shape[:-1], N, device=P.device, dtype=torch.float32)
         ysoft = torch.empty_like(w)
+        sh = current_shard() if expo is None else None
+        if sh is not None:
+            B, T, _ = _bt(P.shape, "gmm_latent")
+            check(lib().mlvae_gmm_latent_fwd_rows(B, T, N, Z, _p(P), P.shape[-1], _p(eps), None, seed,
+                                                  sh.map(B), tau, _p(z), _p(kl), _p(w), _p(ysoft),
+                                                  _stream()), "gmm_latent_fwd_rows")
+            ctx.save_for_backward(P, eps, ysoft)
+            ctx.shape = (N, Z, tau)
+            return z, kl, w
         check(lib().mlvae_gmm_latent_fwd(rows, N, Z, _p(P), P.shape[-1], _p(eps),
                                          _p(expo) if expo is not None else None, seed, 0, tau,
                                          _p(z), _p(kl), _p(w), _p(ysoft), _stream()),

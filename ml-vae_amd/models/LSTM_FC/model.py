@@ -16,7 +16,7 @@ plain fields under the aug_ names when none is configured (ref:src/utils/data_io
 The reference's append(...) passes argument names its scoring function does not take and raises
 at the first batch; the meaning implemented is its sibling w2v_LSTM_FC's (pred_md_lbl_seqs /
 gt_md_lbl_seqs).  The counts follow the loss's length mask (frame t valid iff t < len T in fp32).
-Single GPU, module mode."""
+Module mode; data parallel through models/md_model.py's shard-exact step."""
 from torch import nn
 
 from brain import Stage
@@ -26,7 +26,11 @@ from utils.metric_stats.md_metric_stats import MDMetricStats
 
 
 class SBModel(MDModel):
+    dp_exact = True
     _head_ran = False
+
+    def _dp_lens_field(self, batch, stage):
+        return self._fields(batch, stage)[0]
 
     def on_stage_start(self, stage, epoch=None):
         super().on_stage_start(stage, epoch)
@@ -69,5 +73,6 @@ class SBModel(MDModel):
         feat_lens = batch[feat_key][1]
         # compute_masked_loss: sum(loss * mask) / sum(mask), the length mask over both classes
         loss = ops.masked_mean(predictions["loss_e"], feat_lens)
-        self.stats_loggers["flvl_md_stats"].append_counts(batch["id"], predictions["flvl_md_counts"])
+        self.stats_loggers["flvl_md_stats"].append_counts(
+            batch["id"], predictions["flvl_md_counts"], batch_index=getattr(batch, "global_index", None))
         return loss

@@ -29,6 +29,7 @@ import torch
 from brain import Stage
 from mlvae_hip import ops
 from models.md_model import MDModel
+from utils.data_io import PAD_ID
 from utils.data_utils import apply_lens_to_loss, undo_padding
 from utils.decode_utils import decode_md_device, decoded_lists, raise_decode_err
 from utils.metric_stats.boundary_metric_stats import BoundaryMetricStats
@@ -48,6 +49,7 @@ TRAIN_TARGETS = (Target.PHN_RECOG, Target.B_DETECTOR, Target.VAE)
 
 
 class SBModel(MDModel):
+    dp_exact = True  # data parallel: models/md_model.py's shard-exact step
     noise = None
     _decode_err = None  # the stage's decode error words, OR-ed on the device
 
@@ -71,6 +73,7 @@ class SBModel(MDModel):
             with open(log, "a") as f:
                 f.write(line + "\n")
         self._decode_err = None
+        self._md_results = []  # data parallel: (global batch index, the batch's saved MD results)
         if self.to_run_evaluation(stage):  # the loss stats super() made, plus the MD metrics
             self.stats_loggers["plvl_md_stats"] = MDMetricStats()
             self.stats_loggers["boundary_stats"] = BoundaryMetricStats()
@@ -82,6 +85,16 @@ class SBModel(MDModel):
 
     def on_stage_end(self, stage, stage_loss, epoch=None):
         self._raise_device_errors()
+        if stage == Stage.TEST and self._dp():
+            import torch.distributed as tdist
+            parts = [None] * self.world_size
+            tdist.all_gather_object(parts, self._md_results)
+            if self.rank == 0:  # one writer, in the single-process order (batch, rank)
+                results = {}
+                for _, _, res in sorted(((b, r, res) for r, part in enumerate(parts) for b, res in part),
+                                        key=lambda x: x[:2]):
+                    results.update(res)
+                self._write_md_results(results)
         if self.to_run_evaluation(stage):
             super().on_stage_end(stage, stage_loss, epoch)
 
@@ -160,7 +173,8 @@ class SBModel(MDModel):
         seqs, seq_lens = batch["gt_cnncl_seq"]
         decoded = decode_md_device(predictions, feat_lens, seqs, seq_lens,
                                    prior=batch["prior"][0][0],
-                                   weight=getattr(self.hparams, "dec_weight", 1.0))
+                                   weight=getattr(self.hparams, "dec_weight", 1.0),
+                                   skip_empty=self._dp())  # a short rank slice's fillers
         predictions["decoded_device"] = decoded
         err = decoded[4]
         self._decode_err = err if self._decode_err is None else self._decode_err | err
@@ -192,11 +206,12 @@ class SBModel(MDModel):
             boundary_seqs, _, plvl_md_lbl_seqs = self._decoded_lists(predictions)
             gt_md_lbl_seqs = undo_padding(*batch["plvl_gt_md_lbl_seq"])
             gt_boundary_seqs = undo_padding(*batch["gt_boundary_seq"])
+            bi = getattr(batch, "global_index", None)
             self.stats_loggers["plvl_md_stats"].append(
-                ids=batch["id"], pred_md_lbl_seqs=plvl_md_lbl_seqs, gt_md_lbl_seqs=gt_md_lbl_seqs,
+                ids=batch["id"], batch_index=bi, pred_md_lbl_seqs=plvl_md_lbl_seqs, gt_md_lbl_seqs=gt_md_lbl_seqs,
                 pred_boundary_seqs=boundary_seqs, gt_boundary_seqs=gt_boundary_seqs)
             self.stats_loggers["boundary_stats"].append(
-                ids=batch["id"], predictions=boundary_seqs, targets=gt_boundary_seqs)
+                ids=batch["id"], batch_index=bi, predictions=boundary_seqs, targets=gt_boundary_seqs)
 
         if stage == Stage.TEST:
             self.save_md_result(batch, predictions)
@@ -210,6 +225,8 @@ class SBModel(MDModel):
         self._decoded_lists(predictions)
         results = {}
         for i, utt_id in enumerate(batch["id"]):
+            if utt_id == PAD_ID:  # the filler of a short rank slice: not an utterance
+                continue
             boundary_seq = predictions["decoded_boundary_seq"][i]
             md_lbl_seq = predictions["decoded_plvl_md_lbl_seq"][i]
             n = len(boundary_seq)
@@ -222,7 +239,12 @@ class SBModel(MDModel):
                     assert False
                 entries.append([int(k.item()), start.item(), end.item()])
             results[utt_id] = entries
+        if self._dp():  # gathered and written by rank 0 at the stage's end
+            self._md_results.append((getattr(batch, "global_index", 0), results))
+            return
+        self._write_md_results(results)
 
+    def _write_md_results(self, results):
         save_dir = Path("datasets") / self.hparams.dataset_name / "saved_md_results"
         save_dir.mkdir(parents=True, exist_ok=True)
         save_path = save_dir / f"{self.hparams.model_name}.json"

@@ -20,8 +20,11 @@ has its own noise, as K independent passes have in distribution.  The score-func
 one fused kernel each way (ops.sfl_losses).
 
 ``self.noise`` (tests): as MD_VAE's, with pi_u [K,B,T] and eps_v, eps_g, expo with a leading K.
-Data-parallel runs of this recipe are not covered.
+Data parallel (models/md_model.py's shard-exact step): the K B fold runs under the shard context's
+folded(K) variant, so row k B_l + b draws what the single process draws at row k B_g + b_g.
 """
+import contextlib
+
 from mlvae_hip import ops
 from models.MD_VAE.model import SBModel as MD_VAE
 from models.MD_VAE.model import Target
@@ -45,10 +48,12 @@ class SBModel(MD_VAE):
             # the K draws as one batch of K B utterances
             B, T = pi_logits.shape[:2]
             fold = lambda t: None if t is None else t.reshape(K * B, T, t.shape[-1])
-            enc = self.modules["encoder"](rnn_out.repeat(K, 1, 1), fold(draws),
-                                          eps_v=fold(noise.get("eps_v")), eps_g=fold(noise.get("eps_g")),
-                                          expo=fold(noise.get("expo")))
-            dec = self.modules["decoder"](enc["sampled_h"], feats.repeat(K, 1, 1))
+            sh = ops.current_shard()
+            with (sh.folded(K) if sh is not None else contextlib.nullcontext()):
+                enc = self.modules["encoder"](rnn_out.repeat(K, 1, 1), fold(draws),
+                                              eps_v=fold(noise.get("eps_v")), eps_g=fold(noise.get("eps_g")),
+                                              expo=fold(noise.get("expo")))
+                dec = self.modules["decoder"](enc["sampled_h"], feats.repeat(K, 1, 1))
             recon = dec["losses"]["recon_loss"].view(K, B, T, -1)
             kld = enc["losses"]["vae_kld_loss"].view(K, B, T, -1)
             losses["recon_loss"] = recon.mean(0)

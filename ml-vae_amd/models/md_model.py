@@ -6,6 +6,18 @@ on_stage_end (train_log.txt, checkpoint after VALID with min/max keys, test_outp
 compute_and_save_losses (weights '<key>_weight', default 1 with a warning; '_kld' weights
 divided by 2249 / batch_size).
 
+Data parallel, module mode.  Recipes that set ``dp_exact`` (MD_VAE, MD_VAE_sfl, LSTM_FC) take a
+shard-exact step under world_size > 1: the forward runs inside an ``ops.shard`` context built from
+what the loader attached to the batch (utils/data_io.py), so every draw is the single process's
+for that utterance and every masked mean is this rank's share of the global mean; the '_kld'
+weights use batch_size x world_size; ONE all-reduce (SUM) per training step carries a flat fp32
+bucket = [total loss share | per-key loss shares | the gradients of the parameters that have
+one, in modules.parameters() order].  After it check_gradients, the clip, the running average and
+the loss stats see the global values, so every rank takes the same decisions.  Evaluation sums
+the stacked loss scalars in one small all-reduce per batch; at a stage's end the per-utterance
+scores are gathered and merged into the single-process order (utils/metric_stats).  Replicas
+start from rank 0's weights.  Other recipes in module mode keep ``_dp_mean_grads``.
+
 MI355X path: when the modules are the VAE recipe's (VanillaVAE encoder + Decoder) and the
 optimizer is Adam, init_optimizers builds a mlvae_hip.VAEEngine over the modules'
 parameters and fit_batch / evaluate_batch run the fused HIP step (forward, ELBO, backward,
@@ -29,11 +41,97 @@ N_SAMPLES_KLD = 2249  # the reference's hard-coded corpus size for '_kld' weight
 
 
 class MDModel(Brain):
+    dp_exact = False      # the recipe's data-parallel step is the shard-exact one (see above)
+    _dp_pending = None    # the (key, loss share) pairs of the running DP step
+
     def __init__(self, label_encoder=None, **kwargs):
         super().__init__(**kwargs)
         self.label_encoder = label_encoder
         self.engine = None
         self.stats_loggers = {}
+
+    # ------------------------------------------------------------------ shard-exact data parallel
+    def _dp(self):
+        return self.dp_exact and self.world_size > 1 and self.engine is None
+
+    def _dp_lens_field(self, batch, stage):
+        """The sequence field whose lengths mask the recipe's losses."""
+        return "feat"
+
+    def _dp_shard(self, batch, stage):
+        from mlvae_hip import ops
+        if not hasattr(batch, "global_lens"):
+            raise ValueError("data-parallel step: the batch carries no global lengths (it must come "
+                             "from utils.data_io's loader with world > 1)")
+        lens = batch.global_lens[self._dp_lens_field(batch, stage)]
+        return ops.shard(batch.utt_offset, batch.global_size, lens)
+
+    def _dp_header(self, loss):
+        pending, self._dp_pending = self._dp_pending or [], None
+        vals = [loss.detach().reshape(1).float()] + [v.detach().reshape(1).float() for _, v in pending]
+        return [k for k, _ in pending], vals
+
+    def _dp_log(self, keys, header):
+        """The global per-key losses to the stats loggers (what compute_and_save_losses held back)."""
+        for i, key in enumerate(keys):
+            st = self.stats_loggers.get(key + "_stats")
+            if st is not None:
+                st.append(header[1 + i].clone())  # not a view that keeps the bucket alive
+            else:
+                warnings.warn(f"loss stats logger {key}_stats not found")
+
+    def _fit_batch_dp(self, batch):
+        import torch.distributed as tdist
+        if self.auto_mix_prec:
+            raise ValueError("the shard-exact data-parallel step has no auto_mix_prec mode")
+        opts = list(self.optimizers.values())
+        self._dp_pending = []
+        with self._dp_shard(batch, Stage.TRAIN):
+            outputs = self.compute_forward(batch, Stage.TRAIN)
+            loss = self.compute_objectives(outputs, batch, Stage.TRAIN)
+            loss.backward()
+        keys, vals = self._dp_header(loss)
+        # under a target cycle the parameters without gradient are the same on every rank
+        params = [p for p in self.modules.parameters() if p.grad is not None]
+        flat = torch.cat(vals + [p.grad.reshape(-1) for p in params])
+        tdist.all_reduce(flat)  # SUM: the shares add up to the global batch's loss and gradient
+        off = len(vals)
+        for p in params:
+            n = p.numel()
+            p.grad.copy_(flat[off:off + n].view_as(p.grad))
+            off += n
+        loss = flat[0].clone()
+        self._dp_log(keys, flat)
+        if self.check_gradients(loss):
+            for opt in opts:
+                opt.step()
+        for opt in opts:
+            opt.zero_grad()
+        self.optimizer_step += 1
+        return loss.detach()
+
+    def _evaluate_batch_dp(self, batch, stage):
+        import torch.distributed as tdist
+        self._dp_pending = []
+        with self._dp_shard(batch, stage):
+            out = self.compute_forward(batch, stage=stage)
+            loss = self.compute_objectives(out, batch, stage=stage)
+        keys, vals = self._dp_header(loss)
+        flat = torch.cat(vals)
+        tdist.all_reduce(flat)
+        self._dp_log(keys, flat)
+        return flat[0].clone()
+
+    def _dp_merge_stats(self):
+        """Every rank's per-utterance scores, merged into the single-process order on all ranks
+        (the logged numbers and the checkpoint's meta are then the same everywhere)."""
+        import torch.distributed as tdist
+        for key in sorted(self.stats_loggers):
+            st = self.stats_loggers[key]
+            if hasattr(st, "merge"):
+                states = [None] * self.world_size
+                tdist.all_gather_object(states, st.state())
+                st.merge(states)
 
     # ------------------------------------------------------------------ optimizers
     def _optimizer_infos(self):
@@ -117,6 +215,10 @@ class MDModel(Brain):
                         info = functools.partial(hip_optim.Adam, *info.args, **info.keywords)
                     opt = info(self.modules.parameters())
                 self.optimizers[key] = opt
+            if self._dp():  # replicas start from rank 0's weights
+                import torch.distributed as tdist
+                for p_ in self.modules.parameters():
+                    tdist.broadcast(p_.data, 0)
             if self.auto_mix_prec:
                 # SpeechBrain builds the GradScaler with the Brain, before on_fit_start recovers:
                 # registered here (init_optimizers runs right before recover_if_possible), a
@@ -135,6 +237,8 @@ class MDModel(Brain):
             self._log_losses(loss)
             self.optimizer_step += 1
             return loss[2].detach()
+        if self._dp():
+            return self._fit_batch_dp(batch)
         opts = list(self.optimizers.values())
         if self.auto_mix_prec:
             # ref:src/models/md_model.py:60-76: zero_grad, autocast forward, scaled backward,
@@ -192,6 +296,8 @@ class MDModel(Brain):
                                          epoch=self.hparams.epoch_counter.current)
             self._log_losses(loss)
             return loss[2].detach()
+        if self._dp():
+            return self._evaluate_batch_dp(batch, stage)
         return super().evaluate_batch(batch, stage)
 
     def _engine_inputs(self, batch):
@@ -237,13 +343,20 @@ class MDModel(Brain):
             warnings.warn(f"{weight_key} not found, use 1 as default")
             weight = 1
         if "_kld" in weight_key:
-            weight /= (N_SAMPLES_KLD / self.hparams.batch_size)
+            # the shard-exact data-parallel step: the global batch's size (batch_size is per rank)
+            dp = getattr(self, "_dp", None)
+            world = self.world_size if dp is not None and dp() else 1
+            weight /= (N_SAMPLES_KLD / (self.hparams.batch_size * world))
         return weight
 
     def compute_and_save_losses(self, losses):
         total = 0
         for key, value in losses.items():
             total = total + self._weight_for(key) * value
+            # a data-parallel step: the global value is logged after the reduce (_dp_log)
+            if getattr(self, "_dp_pending", None) is not None:
+                self._dp_pending.append((key, value))
+                continue
             st = self.stats_loggers.get(key + "_stats")
             if st is not None:
                 st.append(value)
@@ -291,6 +404,8 @@ class MDModel(Brain):
         name = stage.name.lower()
         if epoch is None:
             epoch = self.hparams.epoch_counter.current
+        if self._dp():
+            self._dp_merge_stats()
         log = self._collect_metrics(stage_loss)
         if stage in (Stage.TRAIN, Stage.VALID):
             if self.rank == 0:

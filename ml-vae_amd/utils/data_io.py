@@ -16,7 +16,12 @@ Batches follow SpeechBrain's PaddedBatch: batch['feat'] = (padded [B, Tmax, F], 
 of W*bs, padded to that global batch's longest utterance (so every rank sees the single-process
 batch's T and relative lengths).  TRAIN drops an incomplete last global batch (every rank runs
 the same number of optimizer steps); VALID / TEST keep it: ranks whose slice of the remainder is
-short fill it with zero-length utterances, which every masked mean and frame count excludes."""
+short fill it with zero-length utterances (id ``__pad__``), which every masked mean and frame
+count excludes.  Each data-parallel batch also carries, as attributes, what a rank needs to take
+its share of the global batch without a collective: ``global_lens`` ({field: the relative
+lengths of the whole global batch, fillers not among them}), ``utt_offset`` (the global index of
+its first row), ``global_size`` (utterances of the global batch) and ``global_index`` (which
+global batch of the split this is)."""
 import io
 import pickle
 from pathlib import Path
@@ -35,6 +40,9 @@ output_keys = [
 ]
 
 
+PAD_ID = "__pad__"  # the zero-length fillers of a short rank slice (never an utterance: no scores)
+
+
 def _seq_max(items):
     """{field: longest sequence} over the given utterances (tensor fields with a time axis)."""
     out = {}
@@ -47,12 +55,23 @@ def _seq_max(items):
 
 def _empty_like(e):
     """A zero-length utterance with the fields of e (fills a short rank slice in evaluation)."""
-    d = {"id": "__pad__"}
+    d = {"id": PAD_ID}
     for k, v in e.items():
         if k == "id":
             continue
         d[k] = v.new_zeros((0,) + tuple(v.shape[1:])) if torch.is_tensor(v) and v.dim() >= 1 else v
     return d
+
+
+def _global_lens(glob, pad_to):
+    """{field: relative lengths [len(glob)]} of the global batch, as PaddedBatch computes them."""
+    out = {}
+    for k, tmax in pad_to.items():
+        vals = [e[k] for e in glob]
+        if all(torch.is_tensor(v) and v.dim() >= 1 for v in vals):
+            out[k] = torch.tensor([v.shape[0] / tmax if tmax else 0.0 for v in vals],
+                                  dtype=torch.float32)
+    return out
 
 
 def _batched(items, batch_size, rank=0, world=1, stage=None, skip=0):
@@ -68,7 +87,13 @@ def _batched(items, batch_size, rank=0, world=1, stage=None, skip=0):
         glob = items[i:i + g]
         mine = glob[rank * batch_size:(rank + 1) * batch_size]
         mine = mine + [_empty_like(glob[0])] * (batch_size - len(mine))
-        yield PaddedBatch(mine, pad_to=_seq_max(glob))
+        pad_to = _seq_max(glob)
+        batch = PaddedBatch(mine, pad_to=pad_to)
+        batch.global_lens = _global_lens(glob, pad_to)
+        batch.utt_offset = rank * batch_size
+        batch.global_size = len(glob)
+        batch.global_index = i // g
+        yield batch
 
 
 class BatchLoader:

@@ -20,10 +20,13 @@ def _f32(t, dev):
     return t.to(dev, torch.float32).contiguous()
 
 
-def decode_md_device(predictions, feat_lens, plvl_cnnl_seqs, plvl_cnnl_seq_lens, prior, weight=1.0):
+def decode_md_device(predictions, feat_lens, plvl_cnnl_seqs, plvl_cnnl_seq_lens, prior, weight=1.0,
+                     skip_empty=False):
     """The decode with its results left on the device: int32 tensors (boundary [B,T], flvl [B,T],
     plvl [B,L], lens [B,2] = (T_i, L_i), err [1]); -1 past T_i / L_i.  No host sync: the caller
-    reads ``err`` where it syncs anyway (``decoded_lists`` does)."""
+    reads ``err`` where it syncs anyway (``decoded_lists`` does).  skip_empty (data parallel): a
+    row with no frames and no phonemes -- the filler of a short rank slice -- decodes to nothing
+    (-1 everywhere, lens (0, 0)) instead of setting the empty-utterance error bit."""
     logits = predictions["phn_recog_out"]
     if not logits.is_cuda:
         raise RuntimeError("decode_plvl_md_lbl_seqs_full runs on the HIP device only (no CPU fallback)")
@@ -42,9 +45,15 @@ def decode_md_device(predictions, feat_lens, plvl_cnnl_seqs, plvl_cnnl_seq_lens,
     lens = torch.empty(B, 2, device=dev, dtype=torch.int32)
     err = torch.zeros(1, device=dev, dtype=torch.int32)
     P = lambda t: t.data_ptr()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if skip_empty:
+        check(lib().mlvae_viterbi_md_ex(B, T, N, L, P(logits), N, P(bv), P(pil), P(pr), P(seqs), P(fl),
+                                        P(sl), float(weight), 1, P(ws), ws.numel(), P(bnd), P(flvl),
+                                        P(plvl), P(lens), P(err), stream), "viterbi_md_ex")
+        return bnd, flvl, plvl, lens, err
     check(lib().mlvae_viterbi_md(B, T, N, L, P(logits), N, P(bv), P(pil), P(pr), P(seqs), P(fl), P(sl),
                                  float(weight), P(ws), ws.numel(), P(bnd), P(flvl), P(plvl), P(lens),
-                                 P(err), torch.cuda.current_stream(dev).cuda_stream), "viterbi_md")
+                                 P(err), stream), "viterbi_md")
     return bnd, flvl, plvl, lens, err
 
 

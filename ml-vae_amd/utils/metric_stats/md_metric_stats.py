@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from utils.data_utils import boundary_seq_to_seg_seq
-from utils.metric_stats.base_metric_stats import BaseMetricStats
+from utils.metric_stats.base_metric_stats import PAD_ID, BaseMetricStats, drop_pad
 
 EPS = 1e-6
 
@@ -18,10 +18,14 @@ class MDMetricStats(BaseMetricStats):
         super().__init__(metric_fn=batch_seq_md_scoring)
         self.saved_seqs = {}
 
-    def append(self, ids, **kwargs):
+    def append(self, ids, batch_index=None, **kwargs):
         self._require_fn()
+        ids, kwargs = drop_pad(ids, kwargs)
+        if not ids:  # a rank slice of fillers alone
+            self._batches += 1
+            return
         scores, seqs = self.metric_fn(**kwargs)
-        self._extend(ids, scores)
+        self._extend(ids, scores, batch_index)
         seqs["utt_ids"] = ids
         if not self.saved_seqs:
             self.saved_seqs = seqs
@@ -29,18 +33,35 @@ class MDMetricStats(BaseMetricStats):
             for key in self.saved_seqs:
                 self.saved_seqs[key].extend(seqs[key])
 
-    def append_counts(self, ids, counts):
+    def append_counts(self, ids, counts, batch_index=None):
         """The scores of a batch from its [B, 4] integer counts (both correct, both
         mispronounced, missed, false alarm; ops.flvl_md_head's).  A device tensor is kept as it
         is and read once by summarize(): no host sync per batch."""
         if counts.dim() != 2 or counts.shape[1] != 4 or counts.shape[0] != len(ids):
             raise ValueError(f"counts must be [{len(ids)}, 4], got {tuple(counts.shape)}")
-        self._pending.append((list(ids), counts.detach()))
+        self._pending.append((list(ids), counts.detach(), batch_index))
 
     def _flush_counts(self):
         pending, self._pending = self._pending, []
-        for ids, counts in pending:
-            self._extend(ids, counts_md_scoring(counts.cpu()))
+        for ids, counts, batch_index in pending:
+            keep = [i for i, u in enumerate(ids) if u != PAD_ID]
+            counts = counts.cpu()
+            if len(keep) < len(ids):  # the fillers of a short rank slice are not utterances
+                ids, counts = [ids[i] for i in keep], counts[keep]
+            self._extend(ids, counts_md_scoring(counts) if ids else [], batch_index)
+
+    def state(self):
+        self._flush_counts()
+        st = super().state()
+        st["saved_seqs"] = self.saved_seqs
+        return st
+
+    def merge(self, states):
+        perm = super().merge(states)
+        seqs = [st.get("saved_seqs") or {} for st in states]
+        keys = next((list(s) for s in seqs if s), [])
+        self.saved_seqs = {k: [seqs[r][k][n] for r, n in perm] for k in keys}
+        return perm
 
     def clear(self):
         super().clear()
