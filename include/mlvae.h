@@ -736,6 +736,45 @@ int mlvae_apply_weight_bwd(int rows, int N, int C, const float* x, int ldx, cons
                            const float* dy, int lddy, float* dx, int lddx, float* dw,
                            void* stream);
 
+/* Per-utterance scoring of the upstream-module recipes (csrc/score.hip): the integer counts behind
+ * phn_acc.* and boundary.*, left on the device, one workgroup per utterance -- the reference scores
+ * on the host per utterance on every batch (ref:src/models/test_b_ind_classifier/model.py:53-72,
+ * ref:src/utils/metric_stats/phn_acc_metric_stats.py:50-85, ref:src/utils/metric_stats/
+ * boundary_metric_stats.py:58-86).  T_b = round(T feat_lens[b]) and L_b = round(L phn_lens[b]) in
+ * fp32, half to even (undo_padding_tensor's rule, mlvae_phn_bce's); nothing at t >= T_b or l >= L_b
+ * is read.  B == 0 or T == 0 is a no-op returning 0; a null pointer or a negative size gives
+ * status 1.  Each entry zeroes its outputs on the stream first.  Every output is an integer (no
+ * floating-point atomics): a rerun is bit-identical.
+ * mlvae_phn_acc: logits [B,T,C] (row stride ldl, any C >= 1), flvl_tgt [B,T] and plvl_tgt [B,L]
+ *   int64 (plvl_tgt may be NULL, phn_lens and boundary then too), boundary [B,T] floats.  counts[b] =
+ *   (flvl_correct, T_b, plvl_correct, L_b).  flvl_correct: frames t < T_b whose argmax over the
+ *   classes equals flvl_tgt[b,t] (torch.argmax: the first maximal index, a NaN is the maximum; a
+ *   target outside [0, C) never matches).  plvl_correct: the flags == 1 in [0, T_b) open the
+ *   segments, segment k runs to the next flag or T_b; its class sums are fp32 from 0 over the
+ *   frames in increasing t; their argmax is compared with plvl_tgt[b,k].  Bit 128 of *err (the
+ *   reference's two asserts): the flags are not L_b many, or the first is not at frame 0 with
+ *   T_b > 0; that utterance's plvl_correct is 0.  A row with T_b == 0 and L_b == 0 (the filler of
+ *   a short data-parallel slice) gives zeros and no error.  plvl_tgt == NULL: (.., .., 0, 0).
+ * mlvae_boundary_topk: v, fa_boundary [B,T] floats.  k_out[b] = k_b = the entries == 1 of the whole
+ *   padded row of fa_boundary; pred[b,t] int32 = 1 for the k_b largest of v[b, :T_b], 0 for the
+ *   other valid frames, -1 past T_b.  Order: value descending, then index ascending; a NaN ranks
+ *   above every number (torch.topk); frame i is chosen iff fewer than k_b frames precede it.  The
+ *   row is ranked in LDS: T > mlvae_boundary_topk_max_frames() (12288) gives status 1.  k_b > T_b
+ *   sets bit 256 of *err (torch.topk raises) and the row gets no ones.
+ * mlvae_boundary_score: pred [B,T] int32 (mlvae_boundary_topk's, or the decode's boundary_out),
+ *   target [B,T] floats.  counts[b] = (correct, n_pred, n_target) over t < T_b: the frames with
+ *   pred == 1 walked in time order against the true segments [start_s, start_{s+1}] (both ends
+ *   included, the last one ends at T_b): a prediction before the segment is skipped, one inside
+ *   matches and advances both, one past it advances the segment. */
+int mlvae_boundary_topk_max_frames(void);
+int mlvae_phn_acc(int B, int T, int C, int L, const float* logits, int ldl, const float* feat_lens,
+                  const long long* flvl_tgt, const long long* plvl_tgt, const float* phn_lens,
+                  const float* boundary, int* counts, int* err, void* stream);
+int mlvae_boundary_topk(int B, int T, const float* v, const float* feat_lens,
+                        const float* fa_boundary, int* pred, int* k_out, int* err, void* stream);
+int mlvae_boundary_score(int B, int T, const int* pred, const float* target, const float* feat_lens,
+                         int* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

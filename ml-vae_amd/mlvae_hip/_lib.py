@@ -70,6 +70,10 @@ _SIGS = {
     "mlvae_flvl_head_workspace_size": [I, I, I],
     "mlvae_flvl_head_fwd": [I, I, I, P, P, P, P, P, F, F, P, P, P, P, P, P],
     "mlvae_flvl_head_bwd": [I, I, I, P, P, P, P, P, F, F, P, P, P, P, SZ, P],
+    "mlvae_boundary_topk_max_frames": [],
+    "mlvae_phn_acc": [I, I, I, I, P, I, P, P, P, P, P, P, P, P],
+    "mlvae_boundary_topk": [I, I, P, P, P, P, P, P, P],
+    "mlvae_boundary_score": [I, I, P, P, P, P, P],
     "mlvae_lstm1_fwd": [I, I, I, I, P, P, P, P, P, P, SZ, P, P],
     "mlvae_lstm1_bwd": [I, I, I, I, P, P, P, P, P, P, SZ, P, P],
     "mlvae_lstm_gates_fp16": [I, I, I],

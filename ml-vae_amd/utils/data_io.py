@@ -10,6 +10,9 @@
   gt_cnncl_seq, fa_boundary_seq, gt_boundary_seq, plvl_gt_md_lbl_seq, prior -- drawn from a
   generator of their own per utterance, so the features are the same with and without them,
   and flvl_gt_md_lbl_seq (the LSTM_FC baseline's frame-level targets), derived from them.
+  ``phn_labels=True`` (``synthetic.phn_labels``) with it adds flvl_gt_cnncl_seq, the canonical
+  phoneme id of every frame (test_phn_classifier's frame-level targets), derived likewise: it
+  takes no draw, so every other field is the same with and without it.
 
 Batches follow SpeechBrain's PaddedBatch: batch['feat'] = (padded [B, Tmax, F], relative lengths
 [B]).  Under data parallelism rank r of W reads utterances [r*bs, (r+1)*bs) of every global batch
@@ -207,7 +210,7 @@ def _label_generator(seed, index):
     return torch.Generator().manual_seed((int(seed) * 1000003 + index + 1) % (2 ** 63 - 1) + 0x4D44)
 
 
-def _synthetic_md_labels(T, n_phonemes, g):
+def _synthetic_md_labels(T, n_phonemes, g, phn_labels=False):
     """The MD fields of one utterance of T frames (what phn_bce, the Viterbi decode and
     boundary_md_scoring assert: a boundary at frame 0, one boundary per phoneme, ids in range):
     L phonemes, L in [max(2, T // 12), max(2, T // 8)], each at least MIN_SEG frames long."""
@@ -229,19 +232,23 @@ def _synthetic_md_labels(T, n_phonemes, g):
     cnncl = torch.randint(0, n_phonemes, (L,), generator=g, dtype=torch.int64)
     plvl = (torch.rand(L, generator=g) < 0.2).to(torch.int64)
     # frame level: each phoneme's label over its gt_boundary_seq segment (no draw of its own)
-    flvl = plvl[torch.cumsum(gt, 0).to(torch.int64) - 1]
-    return {
+    seg = torch.cumsum(gt, 0).to(torch.int64) - 1
+    flvl = plvl[seg]
+    out = {
         "gt_cnncl_seq": cnncl,
         "fa_boundary_seq": fa,
         "gt_boundary_seq": gt,
         "plvl_gt_md_lbl_seq": plvl,
         "flvl_gt_md_lbl_seq": flvl,
     }
+    if phn_labels:  # each phoneme's canonical id over its gt_boundary_seq segment (no draw either)
+        out["flvl_gt_cnncl_seq"] = cnncl[seg]
+    return out
 
 
 class SyntheticSet:
     def __init__(self, n_utts, feat_dim, min_frames, max_frames, seed, sorting="descending",
-                 md_labels=False, n_phonemes=39):
+                 md_labels=False, n_phonemes=39, phn_labels=False):
         g = torch.Generator().manual_seed(seed)
         lens = torch.randint(min_frames, max_frames + 1, (n_utts,), generator=g)
         self.items = []
@@ -253,7 +260,8 @@ class SyntheticSet:
             # the decode's phoneme prior, in (0.05, 0.5): one per set, carried by every utterance
             prior = 0.06 + 0.43 * torch.rand(n_phonemes + 2, generator=_label_generator(seed, -1))
             for i, e in enumerate(self.items):
-                e.update(_synthetic_md_labels(e["feat"].shape[0], n_phonemes, _label_generator(seed, i)))
+                e.update(_synthetic_md_labels(e["feat"].shape[0], n_phonemes, _label_generator(seed, i),
+                                              phn_labels=phn_labels))
                 e["prior"] = prior.clone()
         _sort(self.items, sorting)
         self.sorting = sorting
@@ -288,5 +296,6 @@ def prepare_datasets(hparams):
                                  d.get("max_frames", 200), hparams.get("seed", 123456) + j,
                                  hparams.get("sorting", "descending"),
                                  md_labels=bool(d.get("md_labels", False)),
-                                 n_phonemes=int(hparams.get("n_phonemes", 39))))
+                                 n_phonemes=int(hparams.get("n_phonemes", 39)),
+                                 phn_labels=bool(d.get("phn_labels", False))))
     return sets, None

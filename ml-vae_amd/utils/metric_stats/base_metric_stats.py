@@ -84,3 +84,39 @@ class BaseMetricStats:
 
     def write_stats(self, f):
         f.write("\t".join(str(v) for v in self.summarize().values()) + "\n")
+
+
+class CountsMixin:
+    """append_counts for a stats class whose scores follow from a few integers per utterance that
+    a kernel left on the device ([B, n_counts] int32): the tensor is kept as it is and read once,
+    by summarize() / state() -- no host sync per batch.  The class names ``n_counts`` and
+    ``counts_fn`` ([b, n_counts] CPU int32 -> one score dict per utterance).  Filler rows
+    (``__pad__``) are dropped; batch_index orders the entries for merge() as append's does."""
+    n_counts = 0
+    counts_fn = None
+
+    def clear(self):
+        super().clear()
+        self._pending = []
+
+    def append_counts(self, ids, counts, batch_index=None):
+        if counts.dim() != 2 or counts.shape[1] != self.n_counts or counts.shape[0] != len(ids):
+            raise ValueError(f"counts must be [{len(ids)}, {self.n_counts}], got {tuple(counts.shape)}")
+        self._pending.append((list(ids), counts.detach(), batch_index))
+
+    def _flush_counts(self):
+        pending, self._pending = self._pending, []
+        for ids, counts, batch_index in pending:
+            keep = [i for i, u in enumerate(ids) if u != PAD_ID]
+            counts = counts.cpu()
+            if len(keep) < len(ids):  # the fillers of a short rank slice are not utterances
+                ids, counts = [ids[i] for i in keep], counts[keep]
+            self._extend(ids, type(self).counts_fn(counts) if ids else [], batch_index)
+
+    def state(self):
+        self._flush_counts()
+        return super().state()
+
+    def summarize(self, field=None):
+        self._flush_counts()
+        return super().summarize(field)

@@ -8,12 +8,16 @@ import numpy as np
 import torch
 
 from utils.data_utils import boundary_seq_to_seg_seq
-from utils.metric_stats.base_metric_stats import PAD_ID, BaseMetricStats, drop_pad
+from utils.metric_stats.base_metric_stats import BaseMetricStats, CountsMixin, drop_pad
 
 EPS = 1e-6
 
 
-class MDMetricStats(BaseMetricStats):
+class MDMetricStats(CountsMixin, BaseMetricStats):
+    """append_counts takes the [B, 4] integer counts (both correct, both mispronounced, missed,
+    false alarm; ops.flvl_md_head's), kept on the device and read once by summarize() / state()."""
+    n_counts = 4
+
     def __init__(self):
         super().__init__(metric_fn=batch_seq_md_scoring)
         self.saved_seqs = {}
@@ -33,25 +37,7 @@ class MDMetricStats(BaseMetricStats):
             for key in self.saved_seqs:
                 self.saved_seqs[key].extend(seqs[key])
 
-    def append_counts(self, ids, counts, batch_index=None):
-        """The scores of a batch from its [B, 4] integer counts (both correct, both
-        mispronounced, missed, false alarm; ops.flvl_md_head's).  A device tensor is kept as it
-        is and read once by summarize(): no host sync per batch."""
-        if counts.dim() != 2 or counts.shape[1] != 4 or counts.shape[0] != len(ids):
-            raise ValueError(f"counts must be [{len(ids)}, 4], got {tuple(counts.shape)}")
-        self._pending.append((list(ids), counts.detach(), batch_index))
-
-    def _flush_counts(self):
-        pending, self._pending = self._pending, []
-        for ids, counts, batch_index in pending:
-            keep = [i for i, u in enumerate(ids) if u != PAD_ID]
-            counts = counts.cpu()
-            if len(keep) < len(ids):  # the fillers of a short rank slice are not utterances
-                ids, counts = [ids[i] for i in keep], counts[keep]
-            self._extend(ids, counts_md_scoring(counts) if ids else [], batch_index)
-
     def state(self):
-        self._flush_counts()
         st = super().state()
         st["saved_seqs"] = self.saved_seqs
         return st
@@ -63,12 +49,7 @@ class MDMetricStats(BaseMetricStats):
         self.saved_seqs = {k: [seqs[r][k][n] for r, n in perm] for k in keys}
         return perm
 
-    def clear(self):
-        super().clear()
-        self._pending = []
-
     def summarize(self, field=None):
-        self._flush_counts()
         means = super().summarize()
         # F1 of the corpus = F1 of the mean PRE and the mean REC, not the mean of the F1s
         pre, rec = means["PRE"], means["REC"]
@@ -126,6 +107,9 @@ def counts_md_scoring(counts):
         rec = hit / (hit + miss + EPS) * 100
         scores.append({"ACC": acc, "PRE": pre, "REC": rec, "F1": 2 * pre * rec / (pre + rec + EPS)})
     return scores
+
+
+MDMetricStats.counts_fn = staticmethod(counts_md_scoring)
 
 
 def compute_boundary_iou(pred_seg_seq, gt_seg_seq):
