@@ -128,6 +128,18 @@ int mlvae_lstm1_fwd(int prec, int B, int T, int H, const float* w_hh, float* gat
 int mlvae_lstm1_bwd(int prec, int B, int T, int H, const float* w_hh, float* gates,
                     const float* cells, const float* dy, void* dg_bf16, void* xbuf, size_t xbytes,
                     int* err, void* stream);
+/* A pair of independent unidirectional stacks of one shape in ONE launch (the joint recipes'
+ * recogniser and detector LSTMs): the layout of mlvae_lstm_fwd_ex / _bwd_ex -- gates [B*T, 8H]
+ * fp32 with stack a in columns [0,4H) and stack b in [4H,8H), cells / y / dy [B*T, 2H] with a
+ * left and b right -- but both halves run forward in time: each half is exactly what
+ * mlvae_lstm1_fwd / _bwd compute for its own w_hh.  Batch-group kernels, same workspace, err
+ * word and batch chunking as mlvae_lstm_fwd. */
+int mlvae_lstm_pair_fwd(int prec, int B, int T, int H, const float* w_hh_a, const float* w_hh_b,
+                        float* gates, float* cells, float* y, void* y_bf16, void* xbuf,
+                        size_t xbytes, int* err, void* stream);
+int mlvae_lstm_pair_bwd(int prec, int B, int T, int H, const float* w_hh_a, const float* w_hh_b,
+                        float* gates, const float* cells, const float* dy, void* dg_bf16,
+                        void* xbuf, size_t xbytes, int* err, void* stream);
 /* Wide-batch recurrence (csrc/lstm_wide.hip): one launch per layer for the whole batch when B is
  * past one batch-group launch (bf16, H = 512).  mlvae_lstm_gates_fp16(B, H, prec) = 1 for such
  * shapes; their gate buffer is IEEE fp16 [B*T, 8H] (half the projection's write and the

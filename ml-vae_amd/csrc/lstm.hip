@@ -13,6 +13,9 @@
 //   its W_hh rows (4*HJ gate rows, interleaved  r = jj*4 + q  so one MFMA lane ends up
 //   holding i,f,g,o of one (unit, utterance)) stay resident in LDS for all T steps;
 //   the cell state c lives in a register of that lane.
+//   dir selects the weight, the column half and the exchange slab, and -- unless the launch is a
+//   pair of independent unidirectional stacks (LstmArgs::paired, mlvae_lstm_pair_*) -- the time
+//   order; a pair runs both halves forward in time.
 //
 // Hand-off (per step, between the workgroups of one (dir, batch group)): the data IS the
 // flag.  Every 8-byte granule of the exchange buffer (4 bf16 or 2 fp32 values) is written by
@@ -77,6 +80,7 @@ __global__ __launch_bounds__(320) void lstm_fwd_kernel(LstmArgs a) {
   const int H = a.H, T = a.T, j0 = js * HJ;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* W = dir ? a.W1 : a.W0;
+  const bool rev = dir && !a.paired;  // time order: dir alone picks weight / columns / slab
   __shared__ int placement;
 
   // wave w owns M-tile w: lane (bi, q) holds gates i,f,g,o of unit 4w+q, utterance bi.
@@ -121,7 +125,7 @@ __global__ __launch_bounds__(320) void lstm_fwd_kernel(LstmArgs a) {
   for (int i = 0; i < 4; ++i) ld0[i] = ld1[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   auto io_gload = [&](int s_, f32x4 (&v)[4]) {
     if (iobv && s_ < T) {
-      const int t_ = dir ? T - 1 - s_ : s_;
+      const int t_ = rev ? T - 1 - s_ : s_;
       const float* p = a.G + ((size_t)iobg * T + t_) * GLD + dir * 4 * H + iog * H + j0;
 #pragma unroll
       for (int i = 0; i < 4; ++i) v[i] = *reinterpret_cast<const f32x4*>(p + 4 * i);
@@ -134,7 +138,7 @@ __global__ __launch_bounds__(320) void lstm_fwd_kernel(LstmArgs a) {
   };
   auto io_store = [&](int s_) {
     if (s_ < 0 || s_ >= T || (DMODE(a) & 1)) return;
-    const int t_ = dir ? T - 1 - s_ : s_;
+    const int t_ = rev ? T - 1 - s_ : s_;
     const float* src = outr + (s_ & 1) * 16 * OUS;
     if (iobv) {  // activated gates of (b, g)
       float v[16];
@@ -182,7 +186,7 @@ __global__ __launch_bounds__(320) void lstm_fwd_kernel(LstmArgs a) {
   float gx[4] = {0.f, 0.f, 0.f, 0.f};
   auto load_gx = [&](int s_) {
     if (valid && s_ < T && !(s_ > 0 && (DMODE(a) & 2048))) {  // bit 11: timing without prefetch
-      const int t_ = dir ? T - 1 - s_ : s_;
+      const int t_ = rev ? T - 1 - s_ : s_;
       const float* gp = a.G + ((size_t)bglob * T + t_) * GLD + dir * 4 * H + j0 + jj;
 #pragma unroll
       for (int g = 0; g < 4; ++g) gx[g] = gp[g * H];
@@ -193,7 +197,7 @@ __global__ __launch_bounds__(320) void lstm_fwd_kernel(LstmArgs a) {
   if (!IOW || wave < 4) {
   for (int s = 0; s < T; ++s) {
     STAMP(0);
-    const int t = dir ? T - 1 - s : s;
+    const int t = rev ? T - 1 - s : s;
     const size_t n = (size_t)bglob * T + t;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     f32x4* red = red0 + (NRED == 2 ? (s & 1) * 4 * MT * 64 : 0);
@@ -382,6 +386,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(LstmArgs a) {
   const int H = a.H, T = a.T, j0 = js * HJ, G4 = 4 * H;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* W = dir ? a.W1 : a.W0;
+  const bool rev = dir && !a.paired;  // time order: dir alone picks weight / columns / slab
 
   // MFMA roles: A = dG (rows = utterances), B = W_hh^T slice (cols = units), K = 4H over 4 waves
   const int bi = lane & 15, q = lane >> 4;
@@ -422,8 +427,8 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(LstmArgs a) {
   for (int u = 0; u < UPT; ++u) { gi[u] = gf[u] = gg[u] = go[u] = cc[u] = cp[u] = dy[u] = dc[u] = 0.f; }
   auto load_cell = [&](int s_) {
     if (bvalid && s_ < T) {
-      const int t_ = dir ? s_ : T - 1 - s_;
-      const int tp_ = dir ? t_ + 1 : t_ - 1;
+      const int t_ = rev ? s_ : T - 1 - s_;
+      const int tp_ = rev ? t_ + 1 : t_ - 1;
       const bool has_prev = tp_ >= 0 && tp_ < T;
       const size_t n_ = (size_t)bglob * T + t_;
       const size_t np_ = (size_t)bglob * T + min(max(tp_, 0), T - 1);
@@ -445,7 +450,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(LstmArgs a) {
   load_cell(0);
   for (int s = 0; s < T; ++s) {
     STAMP(0);
-    const int t = dir ? s : T - 1 - s;          // reverse of the forward processing order
+    const int t = rev ? s : T - 1 - s;          // reverse of the forward processing order
     const size_t n = (size_t)bglob * T + t;
     float* rb = red + (s & 1) * 4 * 16 * RW;
     float dhrec[UPT];
@@ -623,6 +628,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_rs_kernel(LstmArgs a) {
   const int H = a.H, T = a.T, j0 = js * 16;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* W = dir ? a.W1 : a.W0;
+  const bool rev = dir && !a.paired;  // time order: dir alone picks weight / columns / slab
 
   // reduction + cell role: the 8 contiguous lanes pg = 0..7 of one (unit uc, utterance half)
   // each load NPL producers' partials of 8 utterances, then reduce-scatter so that lane pg
@@ -667,8 +673,8 @@ __global__ __launch_bounds__(256) void lstm_bwd_rs_kernel(LstmArgs a) {
   const int j = j0 + uc;
   auto load_cell = [&](int s_, CellIn& c) {
     if (bvalid && s_ < T && !(s_ > 0 && (DMODE(a) & 2048))) {  // bit 11: timing without prefetch
-      const int t_ = dir ? s_ : T - 1 - s_;
-      const int tp_ = dir ? t_ + 1 : t_ - 1;
+      const int t_ = rev ? s_ : T - 1 - s_;
+      const int tp_ = rev ? t_ + 1 : t_ - 1;
       const size_t n_ = (size_t)bglob * T + t_;
       const size_t np_ = (size_t)bglob * T + min(max(tp_, 0), T - 1);
       const float* gp = a.G + n_ * GLD + dir * 4 * H + j;
@@ -684,7 +690,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_rs_kernel(LstmArgs a) {
   // issued, so that poll does not queue behind HBM loads in this wave's memory queue
   auto step = [&](int s, const CellIn& cur, CellIn& fill) -> bool {
     STAMP(0);
-    const int t = dir ? s : T - 1 - s;
+    const int t = rev ? s : T - 1 - s;
     const size_t n = (size_t)bglob * T + t;
     float dhrec = 0.f;
     if (s == 0) load_cell(2, fill);
@@ -834,15 +840,16 @@ __global__ __launch_bounds__(256) void lstm_bwd_rs_kernel(LstmArgs a) {
 __global__ __launch_bounds__(256) void lstm_bwd_step_f32(int B, int T, int H, int ndir, int s,
                                                          const float* W0, const float* W1, float* G,
                                                          const float* Cs, const float* Y, float* dcbuf,
-                                                         unsigned short* dGb) {
+                                                         unsigned short* dGb, int paired) {
   __shared__ float dgp[16][257];
   __shared__ float red[4][16][65];
   const int dir = blockIdx.z, b0 = blockIdx.y * 16, j0 = blockIdx.x * 64;
   const int tid = threadIdx.x, jl = tid & 63, kq = tid >> 6;
   const int j = j0 + jl, K4 = 4 * H;
   const float* W = dir ? W1 : W0;
-  const int t = dir ? s : T - 1 - s;
-  const int tq = dir ? t - 1 : t + 1;  // the step processed before this one
+  const bool rev = dir && !paired;  // time order (see LstmArgs::paired)
+  const int t = rev ? s : T - 1 - s;
+  const int tq = rev ? t - 1 : t + 1;  // the step processed before this one
   const size_t gld = (size_t)K4 * ndir, yld = (size_t)H * ndir;
   float acc[16];
 #pragma unroll
@@ -878,7 +885,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_f32(int B, int T, int H, in
     float* gp = G + n * gld + (size_t)dir * K4 + jj;
     const float gi = gp[0], gf = gp[H], gg = gp[2 * H], go = gp[3 * H];
     const float cc = Cs[n * yld + (size_t)dir * H + jj];
-    const int tp = dir ? t + 1 : t - 1;  // the cell's previous step in forward time
+    const int tp = rev ? t + 1 : t - 1;  // the cell's previous step in forward time
     const float cp = (tp >= 0 && tp < T) ? Cs[((size_t)b * T + tp) * yld + (size_t)dir * H + jj] : 0.f;
     float* dcp = dcbuf + ((size_t)dir * B + b) * H + jj;
     const float dcv = s > 0 ? *dcp : 0.f;
@@ -903,7 +910,7 @@ bool use_stepwise_bwd(int H, int prec) { return prec == PREC_F32 && H > 512; }
 
 int run_bwd_stepwise(int B, int T, int H, int ndir, const float* W0, const float* W1, float* G,
                      const float* Cs, const float* Y, void* xbuf, size_t xbytes, unsigned short* dgb,
-                     hipStream_t st) {
+                     hipStream_t st, int paired) {
   const size_t need = (size_t)ndir * B * H * sizeof(float);
   if (!xbuf || xbytes < need) {
     mlvae_set_error("lstm: exchange workspace too small (need %zu B)", need);
@@ -912,7 +919,7 @@ int run_bwd_stepwise(int B, int T, int H, int ndir, const float* W0, const float
   float* dc = static_cast<float*>(xbuf);
   const dim3 grid((H + 63) / 64, (B + 15) / 16, ndir);
   for (int s = 0; s < T; ++s) {
-    lstm_bwd_step_f32<<<grid, 256, 0, st>>>(B, T, H, ndir, s, W0, W1, G, Cs, Y, dc, dgb);
+    lstm_bwd_step_f32<<<grid, 256, 0, st>>>(B, T, H, ndir, s, W0, W1, G, Cs, Y, dc, dgb, paired);
     MLVAE_CHECK_LAUNCH();
   }
   return 0;
@@ -1062,13 +1069,14 @@ struct WideExtra {  // outputs only the wide kernels write
 int run(bool fwd, int prec, int B, int T, int H, const float* W0, const float* W1, float* G,
         float* Cs, float* Y, void* xbuf, size_t xbytes, int* err, hipStream_t st,
         unsigned short* yb = nullptr, unsigned short* dgb = nullptr, int gates_fp16 = 0,
-        const WideExtra& ex = WideExtra(), int ndir = 2) {
+        const WideExtra& ex = WideExtra(), int ndir = 2, int paired = 0) {
   if (B <= 0 || T <= 0) return 0;
   if (H <= 0 || H % 4 != 0) { mlvae_set_error("lstm: H=%d must be a positive multiple of 4", H); return 1; }
   if (prec != PREC_F32 && prec != PREC_BF16) { mlvae_set_error("lstm: bad prec %d", prec); return 1; }
   // fp16 gates select the wide-batch kernels; fp32 gates the batch-group kernels (chunked)
   const bool wide = gates_fp16 != 0;
   if (ndir != 1 && ndir != 2) { mlvae_set_error("lstm: %d directions", ndir); return 1; }
+  if (paired && (ndir != 2 || wide)) { mlvae_set_error("lstm: a pair is two halves with fp32 gates"); return 1; }
   if (wide && ndir != 2) { mlvae_set_error("lstm: fp16 gates are bidirectional only"); return 1; }
   if (wide && !use_wide(B, H, prec)) {
     mlvae_set_error("lstm: B=%d H=%d prec=%d: fp16 gates only where mlvae_lstm_gates_fp16() = 1", B, H, prec);
@@ -1088,7 +1096,7 @@ int run(bool fwd, int prec, int B, int T, int H, const float* W0, const float* W
     mlvae_set_error("lstm: fused dropout / bias-gradient outputs, Y = NULL only on the wide-batch path");
     return 1;
   }
-  if (!fwd && use_stepwise_bwd(H, prec)) return run_bwd_stepwise(B, T, H, ndir, W0, W1, G, Cs, Y, xbuf, xbytes, dgb, st);
+  if (!fwd && use_stepwise_bwd(H, prec)) return run_bwd_stepwise(B, T, H, ndir, W0, W1, G, Cs, Y, xbuf, xbytes, dgb, st, paired);
   const int bmax = max_batch_per_launch(H, fwd, prec);
   if (bmax < BG) { mlvae_set_error("lstm: H=%d too large for one resident launch", H); return 1; }
   Plan full = make_plan(bmax < B ? bmax : B, H, prec, fwd);
@@ -1105,7 +1113,7 @@ int run(bool fwd, int prec, int B, int T, int H, const float* W0, const float* W
     a.B = bc; a.T = T; a.H = H; a.NB = p.NB; a.NJ = p.NJ; a.HJ = p.HJ; a.Kp = p.Kp; a.K4p = p.K4p;
     a.W0 = W0; a.W1 = W1;
     const size_t gld = (size_t)4 * H * ndir, yld = (size_t)H * ndir;  // row strides
-    a.ndir = ndir;
+    a.ndir = ndir; a.paired = paired;
     a.G = G + (size_t)b0 * T * gld;
     a.Cs = Cs + (size_t)b0 * T * yld;
     a.Y = Y + (size_t)b0 * T * yld;
@@ -1326,6 +1334,25 @@ extern "C" int mlvae_lstm1_bwd(int prec, int B, int T, int H, const float* w_hh,
   return run(false, prec, B, T, H, w_hh, w_hh, gates, const_cast<float*>(cells),
              const_cast<float*>(dy), xbuf, xbytes, err, (hipStream_t)stream, nullptr,
              static_cast<unsigned short*>(dg_bf16), 0, WideExtra(), 1);
+}
+
+// A pair of independent unidirectional stacks of one shape in one launch: the layout of
+// mlvae_lstm_fwd_ex / _bwd_ex (gates [B*T, 8H], cells / y / dy [B*T, 2H]; stack a left, b right),
+// both halves forward in time -- each half is what mlvae_lstm1_fwd / _bwd compute for its w_hh.
+extern "C" int mlvae_lstm_pair_fwd(int prec, int B, int T, int H, const float* w_hh_a,
+                                   const float* w_hh_b, float* gates, float* cells, float* y,
+                                   void* y_bf16, void* xbuf, size_t xbytes, int* err, void* stream) {
+  return run(true, prec, B, T, H, w_hh_a, w_hh_b, gates, cells, y, xbuf, xbytes, err,
+             (hipStream_t)stream, static_cast<unsigned short*>(y_bf16), nullptr, 0, WideExtra(), 2, 1);
+}
+
+extern "C" int mlvae_lstm_pair_bwd(int prec, int B, int T, int H, const float* w_hh_a,
+                                   const float* w_hh_b, float* gates, const float* cells,
+                                   const float* dy, void* dg_bf16, void* xbuf, size_t xbytes,
+                                   int* err, void* stream) {
+  return run(false, prec, B, T, H, w_hh_a, w_hh_b, gates, const_cast<float*>(cells),
+             const_cast<float*>(dy), xbuf, xbytes, err, (hipStream_t)stream, nullptr,
+             static_cast<unsigned short*>(dg_bf16), 0, WideExtra(), 2, 1);
 }
 
 extern "C" int mlvae_lstm_fwd_ex(int prec, int B, int T, int H, const float* w_hh_fwd,

@@ -72,6 +72,10 @@ struct LstmArgs {
   // reverse; zeros at each utterance's first step) -- dW_hh's time-shifted operand pre-shifted,
   // when no other reader takes Yb (the layer below a dropout)
   int yb_prev;
+  // batch-group kernels: 1 = a pair of independent unidirectional stacks -- dir still selects the
+  // weight, the column half and the exchange slab, but both halves run forward in time (0: dir 1
+  // is the reverse direction of a bidirectional layer)
+  int paired;
 };
 
 // XCC (XCD) id of the executing workgroup: s_getreg_b32 HW_REG_XCC_ID (id 20, bits [3:0])

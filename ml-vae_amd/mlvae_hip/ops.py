@@ -590,6 +590,125 @@ def lstm_full(x, lstm_module, train, seed=None):
     return out, (hn, cn)
 
 
+class LSTMPairFn(torch.autograd.Function):
+    """Two independent unidirectional nn.LSTM(batch_first=True) stacks of one shape over the same
+    input (the joint recipes' recogniser and detector, ref:src/modules/phoneme_recognizer.py:13,
+    boundary_detector.py:19): per layer two input-projection GEMMs into the column halves of one
+    G [N, 8H] and ONE paired recurrence launch (mlvae_lstm_pair_fwd / _bwd), so the two stacks'
+    latency-bound step chains overlap.  No dropout inside a paired stack.  weights = the
+    layer-major list [w_ih, w_hh, b_ih, b_hh] of stack a + the same of stack b, * L."""
+
+    @staticmethod
+    def forward(ctx, x, H, L, *weights):
+        x = _need(x, "lstm input")
+        B, T, _ = x.shape
+        N = B * T
+        l = lib()
+        xbuf, err = _lstm_ws(B, H)
+        saved, inputs = [], []
+        h = x
+        for li in range(L):
+            w = [_need(t, "lstm weight") for t in weights[8 * li:8 * li + 8]]
+            # layer 0: both stacks read x; above it stack s reads its own half of Y (lda = 2H)
+            din, lda = (h.shape[-1], h.shape[-1]) if li == 0 else (H, 2 * H)
+            G = torch.empty(N, 8 * H, device=x.device, dtype=torch.float32)
+            for s in range(2):
+                wi, _, bi, bh = w[4 * s:4 * s + 4]
+                gemm(0, 1, N, 4 * H, din, _p(h, H * s if li else 0), lda, _p(wi), din,
+                     _p(G, 4 * H * s), 8 * H, bias1=_p(bi), bias2=_p(bh))
+            Cs = torch.empty(N, 2 * H, device=x.device, dtype=torch.float32)
+            Y = torch.empty(B, T, 2 * H, device=x.device, dtype=torch.float32)
+            check(l.mlvae_lstm_pair_fwd(_prec(), B, T, H, _p(w[1]), _p(w[5]), _p(G), _p(Cs), _p(Y), None,
+                                        _p(xbuf), xbuf.numel() * 4, _p(err), _stream()), "lstm_pair_fwd")
+            inputs.append(h)
+            saved += [G, Cs, Y]
+            h = Y
+        ctx.save_for_backward(*inputs, *saved, *weights)
+        ctx.H, ctx.L = H, L
+        ctx.set_materialize_grads(False)  # an output outside the loss arrives as None
+        return h[..., :H].contiguous(), h[..., H:].contiguous()
+
+    @staticmethod
+    def backward(ctx, dya, dyb):
+        H, L = ctx.H, ctx.L
+        GL = 8 * H
+        t = ctx.saved_tensors
+        inputs, saved, weights = t[:L], t[L:4 * L], t[4 * L:]
+        B, T = inputs[0].shape[0], inputs[0].shape[1]
+        N = B * T
+        dev = inputs[0].device
+        dy = torch.zeros(B, T, 2 * H, device=dev, dtype=torch.float32)
+        for s, g in enumerate((dya, dyb)):
+            if g is not None:
+                dy[..., H * s:H * (s + 1)] = _need(g, "lstm grad")
+        l = lib()
+        xbuf, err = _lstm_ws(B, H)
+        dW = [None] * len(weights)
+        dx = None
+        for li in range(L - 1, -1, -1):
+            G, Cs, Y = saved[3 * li:3 * li + 3]
+            w = weights[8 * li:8 * li + 8]
+            xin = inputs[li]
+            din, ldx = (xin.shape[-1], xin.shape[-1]) if li == 0 else (H, 2 * H)
+            check(l.mlvae_lstm_pair_bwd(_prec(), B, T, H, _p(w[1]), _p(w[5]), _p(G), _p(Cs), _p(dy), None,
+                                        _p(xbuf), xbuf.numel() * 4, _p(err), _stream()), "lstm_pair_bwd")
+            if li > 0:  # the dgrads fill the column halves of the layer below's dy
+                dx = torch.empty(B, T, 2 * H, device=dev, dtype=torch.float32)
+            elif ctx.needs_input_grad[0]:  # dx = dx_a + dx_b
+                dx = torch.empty(B, T, din, device=dev, dtype=torch.float32)
+            else:
+                dx = None
+            for s in range(2):
+                wi = w[4 * s]
+                if li > 0:
+                    gemm(0, 0, N, H, 4 * H, _p(G, 4 * H * s), GL, _p(wi), H, _p(dx, H * s), 2 * H)
+                elif dx is not None:
+                    gemm(0, 0, N, din, 4 * H, _p(G, 4 * H * s), GL, _p(wi), din, _p(dx), din,
+                         beta=1.0 if s else 0.0)
+                gwi = torch.empty_like(wi)
+                gemm(1, 0, 4 * H, din, N, _p(G, 4 * H * s), GL, _p(xin, H * s if li else 0), ldx,
+                     _p(gwi), din)
+                gwh = torch.empty_like(w[4 * s + 1])
+                # dW_hh = sum_t dG_t^T h_{t-1}: both stacks run forward in time
+                gemm(1, 0, 4 * H, H, N, _p(G, 4 * H * s), GL, _p(Y, H * s), 2 * H, _p(gwh), H,
+                     kshift_T=T, kshift=-1)
+                gbi = torch.empty_like(w[4 * s + 2])
+                gbh = torch.empty_like(w[4 * s + 3])
+                colsum(N, 4 * H, _p(G, 4 * H * s), GL, _p(gbi), _p(gbh))
+                base = 8 * li + 4 * s
+                dW[base:base + 4] = [gwi, gwh, gbi, gbh]
+            dy = dx
+        if int(err.item()) != 0:
+            raise RuntimeError("LSTM recurrence hand-off timed out")
+        return (dx, None, None, *dW)
+
+
+def lstm_pair_ok(lstm_a, lstm_b, train):
+    """True where lstm_pair can run the two modules as one paired recurrence."""
+    for m in (lstm_a, lstm_b):
+        if not isinstance(m, torch.nn.LSTM) or not m.batch_first or m.bidirectional or m.proj_size:
+            return False
+    if (lstm_a.input_size, lstm_a.hidden_size, lstm_a.num_layers) != \
+            (lstm_b.input_size, lstm_b.hidden_size, lstm_b.num_layers):
+        return False
+    if lstm_a.hidden_size % 4:
+        return False
+    return not train or (float(lstm_a.dropout) == 0.0 and float(lstm_b.dropout) == 0.0)
+
+
+def lstm_pair(x, lstm_a, lstm_b, train):
+    """Two unidirectional nn.LSTMs of one shape over the same input x, their recurrences paired
+    in one launch per layer: (out_a, out_b), each [B, T, H]."""
+    if not lstm_pair_ok(lstm_a, lstm_b, train):
+        raise ValueError("lstm_pair: two batch_first unidirectional nn.LSTMs of equal input_size, "
+                         "hidden_size (a multiple of 4) and num_layers, without projection and "
+                         "without dropout in training")
+    H, L = lstm_a.hidden_size, lstm_a.num_layers
+    weights = [getattr(m, f"{kind}_l{li}") for li in range(L) for m in (lstm_a, lstm_b)
+               for kind in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+    return LSTMPairFn.apply(x, H, L, *weights)
+
+
 def bilstm(x, lstm_module, train):
     """The decoder's bidirectional nn.LSTM (ref:src/modules/decoder.py:22)."""
     return lstm(x, lstm_module, train)

@@ -6,7 +6,8 @@ on_stage_end (train_log.txt, checkpoint after VALID with min/max keys, test_outp
 compute_and_save_losses (weights '<key>_weight', default 1 with a warning; '_kld' weights
 divided by 2249 / batch_size).
 
-Data parallel, module mode.  Recipes that set ``dp_exact`` (MD_VAE, MD_VAE_sfl, LSTM_FC) take a
+Data parallel, module mode.  Recipes that set ``dp_exact`` (MD_VAE, MD_VAE_sfl, the joint
+variants, LSTM_FC) take a
 shard-exact step under world_size > 1: the forward runs inside an ``ops.shard`` context built from
 what the loader attached to the batch (utils/data_io.py), so every draw is the single process's
 for that utterance and every masked mean is this rank's share of the global mean; the '_kld'

@@ -21,8 +21,11 @@ class BoundaryDetector(nn.Module):
         self.fc_alpha = nn.Sequential(FCBlock(fc_sizes), nn.Softplus())
         self.fc_beta = nn.Sequential(FCBlock(fc_sizes), nn.Softplus())
 
-    def forward(self, x, feat_lens, boundary_seqs, uniform_u=None):
-        rnn_out = ops.lstm(x, self.rnn, self.training)
+    def forward(self, x, feat_lens, boundary_seqs, uniform_u=None, rnn_out=None):
+        """rnn_out: self.rnn's output computed by the caller (ops.lstm_pair runs it together with
+        the phoneme recogniser's), used in place of this module's own recurrence."""
+        if rnn_out is None:
+            rnn_out = ops.lstm(x, self.rnn, self.training)
         za = torch.squeeze(self.fc_alpha[0](rnn_out), dim=-1)  # pre-Softplus heads, (B, T)
         zb = torch.squeeze(self.fc_beta[0](rnn_out), dim=-1)
         v, bce, kld = ops.boundary_heads(za.contiguous(), zb.contiguous(), boundary_seqs, uniform_u)

@@ -20,8 +20,11 @@ class PhonemeRecognizer(nn.Module):
         self.fc = FCBlock(fc_sizes)
         self.n_phonemes = n_phonemes
 
-    def forward(self, feats, feat_lens, plvl_cnnl_phn_seqs, plvl_cnnl_phn_seq_lens, boundary_seqs):
-        out = ops.lstm(feats, self.rnn, self.training)
+    def forward(self, feats, feat_lens, plvl_cnnl_phn_seqs, plvl_cnnl_phn_seq_lens, boundary_seqs,
+                rnn_out=None):
+        """rnn_out: self.rnn's output computed by the caller (ops.lstm_pair runs it together with
+        the boundary detector's), used in place of this module's own recurrence."""
+        out = ops.lstm(feats, self.rnn, self.training) if rnn_out is None else rnn_out
         out = self.fc(out)
         losses = self.compute_losses(out, feat_lens, plvl_cnnl_phn_seqs, plvl_cnnl_phn_seq_lens,
                                      boundary_seqs)
