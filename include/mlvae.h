@@ -748,6 +748,41 @@ int mlvae_apply_weight_bwd(int rows, int N, int C, const float* x, int ldx, cons
                            const float* dy, int lddy, float* dx, int lddx, float* dw,
                            void* stream);
 
+/* The Hierarchical VAE's latent stretch in one launch (csrc/hvae.hip; replaces, for the recipes that
+ * ask for it, mlvae_reparam_kl_fwd + mlvae_gmm_latent_fwd + the eight mlvae_apply_weight_fwd calls
+ * of ref:src/modules/h_vae.py:21-72, and their backwards).  fp32.
+ *   ml [rows, ldml] = [mean_v | log_var_v] (ldml >= 2Z), P [rows, ldp] as mlvae_gmm_latent_fwd's,
+ *   pi [rows, 2], eps_v [rows, Z], eps_g [rows, N*Z], expo [rows, N] or NULL: Philox(seed,
+ *   offset + r*N + n), the draws of mlvae_gmm_latent_fwd.
+ * Forward: v = (mean_v, log_var_v, eps_v e^{lv_v/2} + mean_v, KL_v) (mlvae_reparam_kl_fwd's),
+ *   g[n] = (m[n], lv[n], z[n], kl[n]) and w, ysoft as mlvae_gmm_latent_fwd's (w bit for bit),
+ *   G = sum_n w[n] g[n] (n ascending), (mean, log_var, h, kl) [rows, Z] = pi0 v + pi1 G.
+ *   ml == NULL && pi == NULL: the GMM-only mode, h = G_z and kl = G_kl; mean, log_var, eps_v unread.
+ * Backward: recomputes v and g from the saved inputs, w and ysoft; cotangents d_mean, d_log_var,
+ *   d_h, d_kl [rows, Z] and d_w [rows, N], each NULL = 0 (the GMM-only mode ignores d_mean and
+ *   d_log_var); writes dml [rows, 2Z], the 4NZ + N columns of dP [rows, lddp] and dpi [rows, 2]
+ *   (dpi may be NULL; dml and dpi are unwritten in the GMM-only mode).  The weight cotangent
+ *   d_w[n] + pi1 sum_key sum_c d_key[c] g_key[n,c] reaches the logits through ysoft (straight-
+ *   through).  Sums over c are fixed-order reductions inside a wave: a rerun is bit-identical.
+ * Any Z >= 1, 1 <= N <= 64, any rows >= 0 (0: a no-op).  Status 1 before any launch: N out of
+ * range, ldp (lddp) < 4NZ + N, ldml < 2Z, exactly one of ml / pi NULL, a required pointer NULL.
+ * mlvae_hvae_latent_fwd_rows: the forward over the rows = B T frames of a data-parallel shard, map
+ *   as mlvae_gmm_latent_fwd_rows' (NULL: the identity, then mlvae_hvae_latent_fwd at offset 0). */
+int mlvae_hvae_latent_fwd(int rows, int N, int Z, const float* ml, int ldml, const float* P, int ldp,
+                          const float* pi, const float* eps_v, const float* eps_g, const float* expo,
+                          unsigned long long seed, unsigned long long offset, float tau, float* mean,
+                          float* log_var, float* h, float* kl, float* w, float* ysoft, void* stream);
+int mlvae_hvae_latent_fwd_rows(int B, int T, int N, int Z, const float* ml, int ldml, const float* P,
+                               int ldp, const float* pi, const float* eps_v, const float* eps_g,
+                               const float* expo, unsigned long long seed, const long long* map,
+                               float tau, float* mean, float* log_var, float* h, float* kl, float* w,
+                               float* ysoft, void* stream);
+int mlvae_hvae_latent_bwd(int rows, int N, int Z, const float* ml, int ldml, const float* P, int ldp,
+                          const float* pi, const float* eps_v, const float* eps_g, const float* w,
+                          const float* ysoft, float tau, const float* d_mean, const float* d_log_var,
+                          const float* d_h, const float* d_kl, const float* d_w, float* dml, float* dP,
+                          int lddp, float* dpi, void* stream);
+
 /* Per-utterance scoring of the upstream-module recipes (csrc/score.hip): the integer counts behind
  * phn_acc.* and boundary.*, left on the device, one workgroup per utterance -- the reference scores
  * on the host per utterance on every batch (ref:src/models/test_b_ind_classifier/model.py:53-72,

@@ -139,6 +139,9 @@ _SIGS = {
     "mlvae_gmm_latent_bwd": [I, I, I, P, I, P, P, F, P, P, P, P, I, P],
     "mlvae_apply_weight_fwd": [I, I, I, P, I, P, P, I, P],
     "mlvae_apply_weight_bwd": [I, I, I, P, I, P, P, I, P, I, P, P],
+    "mlvae_hvae_latent_fwd": [I, I, I, P, I, P, I, P, P, P, P, U64, U64, F, P, P, P, P, P, P, P],
+    "mlvae_hvae_latent_fwd_rows": [I, I, I, I, P, I, P, I, P, P, P, P, U64, P, F, P, P, P, P, P, P, P],
+    "mlvae_hvae_latent_bwd": [I, I, I, P, I, P, I, P, P, P, P, P, F, P, P, P, P, P, P, P, I, P, P],
     "mlvae_lstm_launch_workgroups": [I, I, I, I],
     "mlvae_lstm_set_debug": [P],
     "mlvae_lstm_set_debug_mode": [I],

@@ -51,7 +51,7 @@ def _prec():
 class shard:
     """Context: the batch inside the block is a data-parallel shard of a global batch of
     B_global utterances, its first utterance at utt_offset.  Every drawing op (randn, the LSTM's
-    inter-layer dropout, boundary_heads, pi_sample, pi_sample_k, GmmLatentFn) then draws, for
+    inter-layer dropout, boundary_heads, pi_sample, pi_sample_k, GmmLatentFn, HvaeLatentFn) then draws, for
     each of its utterances, bit for bit what the single process draws for that utterance of the
     global batch (include/mlvae.h, "the random streams over an utterance map"): the ops take the
     seeds from torch's CPU generator as they always do, so ranks seeded alike that make the same
@@ -1275,3 +1275,102 @@ def apply_weight(x, weight):
     """(B,T,N*C) or (B,T,N,C) weighted by (B,T,N) -> (B,T,C)."""
     B, T, N = weight.shape
     return ApplyWeightFn.apply(x.reshape(B, T, -1), weight)
+
+
+class HvaeLatentFn(torch.autograd.Function):
+    """The H-VAE's latent stretch in one launch (csrc/hvae.hip; ref:src/modules/h_vae.py:21-72):
+    ml = [mean_v | log_var_v], P = the GMM's stacked heads, pi [.., 2] -> the mixed (mean, log_var,
+    sampled_h, kl) [.., Z] and the hard Gumbel-softmax weights [.., N].  ml = pi = None is the
+    GMM-only mode: (None, None, collapsed h, collapsed kl, weights).  expo = the Exp(1) draws
+    [.., N] (None: library Philox under `seed`, mapped inside an ops.shard context)."""
+
+    @staticmethod
+    def forward(ctx, ml, P, pi, eps_v, eps_g, expo, N, Z, tau, seed):
+        hier = ml is not None
+        ctx.set_materialize_grads(False)  # an unused output's cotangent reaches the kernel as NULL
+        P, eps_g = _need(P, "gmm heads"), _need(eps_g, "eps_g")
+        expo = _need(expo, "expo") if expo is not None else None
+        if hier:
+            ml, pi, eps_v = _need(ml, "ml"), _need(pi, "pi"), _need(eps_v, "eps_v")
+        rows = _rows(P)
+        lead = P.shape[:-1]
+        new = lambda n: torch.empty(*lead, n, device=P.device, dtype=torch.float32)
+        h, kl, w, ysoft = new(Z), new(Z), new(N), new(N)
+        mean, log_var = (new(Z), new(Z)) if hier else (None, None)
+        nz = lambda t: _p(t) if t is not None else None
+        ldml = ml.shape[-1] if hier else 0
+        sh = current_shard() if expo is None else None
+        if sh is not None:
+            B, T, _ = _bt(P.shape, "hvae_latent")
+            check(lib().mlvae_hvae_latent_fwd_rows(
+                B, T, N, Z, nz(ml), ldml, _p(P), P.shape[-1], nz(pi), nz(eps_v), _p(eps_g), None, seed,
+                sh.map(B), tau, nz(mean), nz(log_var), _p(h), _p(kl), _p(w), _p(ysoft), _stream()),
+                "hvae_latent_fwd_rows")
+        else:
+            check(lib().mlvae_hvae_latent_fwd(
+                rows, N, Z, nz(ml), ldml, _p(P), P.shape[-1], nz(pi), nz(eps_v), _p(eps_g), nz(expo),
+                seed, 0, tau, nz(mean), nz(log_var), _p(h), _p(kl), _p(w), _p(ysoft), _stream()),
+                "hvae_latent_fwd")
+        ctx.hier = hier
+        ctx.save_for_backward(*((ml, pi, eps_v) if hier else ()), P, eps_g, w, ysoft)
+        ctx.shape = (N, Z, tau)
+        return mean, log_var, h, kl, w
+
+    @staticmethod
+    def backward(ctx, d_mean, d_log_var, d_h, d_kl, d_w):
+        if ctx.hier:
+            ml, pi, eps_v, P, eps_g, w, ysoft = ctx.saved_tensors
+        else:
+            (P, eps_g, w, ysoft), ml, pi, eps_v = ctx.saved_tensors, None, None, None
+        N, Z, tau = ctx.shape
+        nz = lambda t: _p(t) if t is not None else None
+        keep =[None if t is None else _need(t, "grad") for t in (d_mean, d_log_var, d_h, d_kl, d_w)]
+        dP = torch.empty_like(P)
+        if P.shape[-1] > 4 * N * Z + N:
+            dP[..., 4 * N * Z + N:] = 0  # columns past the heads: never written by the kernel
+        dml = torch.empty(*P.shape[:-1], 2 * Z, device=P.device, dtype=torch.float32) if ctx.hier else None
+        dpi = torch.empty_like(pi) if ctx.hier and ctx.needs_input_grad[2] else None
+        check(lib().mlvae_hvae_latent_bwd(
+            _rows(P), N, Z, nz(ml), ml.shape[-1] if ctx.hier else 0, _p(P), P.shape[-1], nz(pi),
+            nz(eps_v), _p(eps_g), _p(w), _p(ysoft), tau, *[nz(t) for t in keep], nz(dml), _p(dP),
+            P.shape[-1], nz(dpi), _stream()), "hvae_latent_bwd")
+        if ctx.hier and ml.shape[-1] != 2 * Z:
+            wide = torch.zeros_like(ml)
+            wide[..., :2 * Z] = dml
+            dml = wide
+        return dml, dP, dpi, None, None, None, None, None, None, None
+
+
+def _latent_shapes(what, P, eps_g, expo, N, Z):
+    if not (1 <= N <= 64) or Z < 1:
+        raise ValueError(f"{what}: N must be in [1, 64] and Z >= 1, got N={N} Z={Z}")
+    if P.shape[-1] < 4 * N * Z + N:
+        raise ValueError(f"{what}: the stacked heads need {4 * N * Z + N} columns, got {tuple(P.shape)}")
+    lead = tuple(P.shape[:-1])
+    if tuple(eps_g.shape) != lead + (N * Z,):
+        raise ValueError(f"{what}: eps_g {tuple(eps_g.shape)} is not {lead + (N * Z,)}")
+    if expo is not None and tuple(expo.shape) != lead + (N,):
+        raise ValueError(f"{what}: expo {tuple(expo.shape)} is not {lead + (N,)}")
+    return lead
+
+
+def hvae_latent(ml, P, pi, eps_v, eps_g, expo, N, Z, tau, seed):
+    """(mean, log_var, sampled_h, kl) [.., Z] and gmm_weight [.., N] of the Hierarchical VAE from
+    its two encoders' head outputs, one launch each way (HvaeLatentFn)."""
+    lead = _latent_shapes("hvae_latent", P, eps_g, expo, N, Z)
+    if ml is None or pi is None or eps_v is None:
+        raise ValueError("hvae_latent: ml, pi and eps_v are required (gmm_collapsed is the GMM-only form)")
+    if tuple(ml.shape[:-1]) != lead or ml.shape[-1] < 2 * Z:
+        raise ValueError(f"hvae_latent: ml {tuple(ml.shape)} is not {lead} + (>= {2 * Z},)")
+    if tuple(pi.shape) != lead + (2,):
+        raise ValueError(f"hvae_latent: pi {tuple(pi.shape)} is not {lead + (2,)}")
+    if tuple(eps_v.shape) != lead + (Z,):
+        raise ValueError(f"hvae_latent: eps_v {tuple(eps_v.shape)} is not {lead + (Z,)}")
+    return HvaeLatentFn.apply(ml, P, pi, eps_v, eps_g, expo, N, Z, tau, seed)
+
+
+def gmm_collapsed(P, eps, expo, N, Z, tau, seed):
+    """(weighted_h, weighted_loss) [.., Z] and gmm_weight [.., N] of the GMM-VAE: apply_weight of
+    GmmLatentFn's sampled_h and loss with its own weights, in one launch each way."""
+    _latent_shapes("gmm_collapsed", P, eps, expo, N, Z)
+    return HvaeLatentFn.apply(None, P, None, None, eps, expo, N, Z, tau, seed)[2:]

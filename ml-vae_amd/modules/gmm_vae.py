@@ -32,7 +32,8 @@ class GMMVAE(nn.Module):
         return (self.prior_mean_fc, self.prior_log_var_fc, self.mean_fc, self.log_var_fc,
                 self.gmm_weight_fc)
 
-    def forward(self, feats, eps=None, expo=None):  # feats (B, T, C)
+    def stacked_heads(self, feats):
+        """P (B, T, 4NZ + N) = [prior_mean | prior_log_var | mean | log_var | gmm logits]."""
         h = feats
         plan = self.fc[0].linear_plan()
         for i, (lin, act) in enumerate(plan):
@@ -40,12 +41,29 @@ class GMMVAE(nn.Module):
         heads = self._heads()
         W = torch.cat([m.weight for m in heads], 0)
         b = torch.cat([m.bias for m in heads], 0)
-        P = ops.linear(h, W, b)  # (B, T, 4NZ + N)
+        return ops.linear(h, W, b)
+
+    def draws(self, P, eps, expo):
+        """(eps, Gumbel seed): torch's RNG is read for eps first, then for the seed."""
+        if eps is None:
+            eps = ops.randn(P.shape[:-1] + (self.num_components * self.latent_size,))
+        seed = 0 if expo is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+        return eps, seed
+
+    def collapsed(self, feats, eps=None, expo=None):
+        """apply_weight(sampled_h, gmm_weight), apply_weight(loss, gmm_weight) and gmm_weight from
+        one kernel (ops.gmm_collapsed): what models/test_gmm_vae reads of this encoder.  Same
+        draws as forward under the same torch seed."""
+        P = self.stacked_heads(feats)
+        eps, seed = self.draws(P, eps, expo)
+        h, kl, w = ops.gmm_collapsed(P, eps, expo, self.num_components, self.latent_size, TAU, seed)
+        return {"weighted_h": h, "weighted_loss": kl, "gmm_weight": w}
+
+    def forward(self, feats, eps=None, expo=None):  # feats (B, T, C)
+        P = self.stacked_heads(feats)  # (B, T, 4NZ + N)
         N, Z = self.num_components, self.latent_size
         NZ = N * Z
-        if eps is None:
-            eps = ops.randn(P.shape[:-1] + (NZ,))
-        seed = 0 if expo is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+        eps, seed = self.draws(P, eps, expo)
         z, kl, w = ops.GmmLatentFn.apply(P, eps, expo, N, Z, TAU, seed)
         return {
             "prior_mean": P[..., :NZ],

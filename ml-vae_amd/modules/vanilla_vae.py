@@ -20,13 +20,17 @@ class VanillaVAE(nn.Module):
         self.log_var_fc = nn.Linear(fc_sizes[-1], latent_size)
         self.latent_size = latent_size
 
-    def forward(self, feats, eps=None):  # feats (B, T, C)
+    def mean_logvar(self, feats):
+        """ml (B, T, 2Z) = [mean | log_var]."""
         h = feats
         plan = self.fc[0].linear_plan()
         for i, (lin, act) in enumerate(plan):
             # the outer LeakyReLU (self.fc[1]) folds into the last FCBlock layer's epilogue
             h = ops.linear(h, lin.weight, lin.bias, act or i == len(plan) - 1)
-        ml = _mean_logvar(h, self.mean_fc, self.log_var_fc)  # [.., 2Z] = [mean | log_var]
+        return _mean_logvar(h, self.mean_fc, self.log_var_fc)
+
+    def forward(self, feats, eps=None):  # feats (B, T, C)
+        ml = self.mean_logvar(feats)  # [.., 2Z] = [mean | log_var]
         if eps is None:
             eps = ops.randn(ml.shape[:-1] + (self.latent_size,))
         z, kl = ops.ReparamKLFn.apply(ml, eps)
