@@ -822,6 +822,61 @@ int mlvae_boundary_topk(int B, int T, const float* v, const float* feat_lens,
 int mlvae_boundary_score(int B, int T, const int* pred, const float* target, const float* feat_lens,
                          int* counts, void* stream);
 
+/* The sequence lattice of the HMM_DNN_ALI aligner (csrc/align.hip; ref:src/models/HMM_DNN_ALI/
+ * model.py:47-91): forward-backward and Viterbi over a per-utterance left-to-right state chain.
+ * pout [B,T,C] fp32 log-probabilities (row stride ld), lens / phn_lens [B] relative lengths, phns
+ * [B,L] int64.  T_b = rintf(T lens[b]), L_b = rintf(L phn_lens[b]) (fp32, half to even, clamped);
+ * nothing at t >= T_b or l >= L_b is read.  Phoneme p expands into spp >= 1 states with emission
+ * classes p spp + j: U_b = spp L_b states.  topology 0 (HMM): nodes = states, a path starts in
+ * node 0, stays or moves to the next node, ends in node U_b - 1.  topology 1 (CTC): blank, s_0,
+ * blank, .., blank (2 U_b + 1 nodes), stay / next / skip over a blank between two different
+ * classes, start in node 0 or 1, end in one of the last two.  A path scores the sum of its
+ * emissions.  A chain may have mlvae_lattice_max_nodes() (1024) nodes, counted on the padded L:
+ * beyond it, status 1.
+ * *err bits (device word, OR-ed): 512 = HMM chain infeasible (T_b < U_b, U_b = 0 or T_b = 0);
+ *   1024 = a phoneme id whose state class is outside [0, C); 2048 = CTC, a target class equal to
+ *   blank.  Such an utterance scores 0 with gradient 0 and alignment -1.  A CTC chain without a
+ *   path is no error: score 0, gradient 0 (torch's zero_infinity).
+ * mlvae_lattice_fb: score[b] = log sum over the paths of exp(path score); alpha (and, with
+ *   need_beta, beta: the chain run backwards, concurrently) go to the workspace (fp32, renormalised
+ *   every few frames; mlvae_lattice_workspace_size bytes), which mlvae_lattice_grad reads.
+ * mlvae_lattice_grad: dpout[b,t,c] (row stride ldd) = g[b] sum_{node n of class c} gamma_t(n), gamma
+ *   the posterior occupancy: the partial derivative of g . score with respect to pout (not torch's
+ *   ctc_loss gradient, which folds the log-softmax in).  The nodes of a class are summed in
+ *   ascending node order, no floating-point atomics: a rerun is bit-identical.  Exactly 0 for
+ *   classes without a node, frames t >= T_b and utterances without a score.  Same arguments as the
+ *   mlvae_lattice_fb call (need_beta = 1) that filled ws.
+ * mlvae_hmm_viterbi: HMM topology.  vscore[b] = the best path's score (float64 sums of the fp32
+ *   emissions, rounded once), align[b,t] int32 = its state position in [0, U_b), -1 for t >= T_b;
+ *   a tie keeps "stay".  ws: mlvae_hmm_viterbi_workspace_size bytes (the backpointers).
+ * mlvae_align_counts: counts[b] = (frames correct, T_b): frame t < T_b is correct iff
+ *   phns[b, align[b,t] / spp] equals phns[b,k], k the first phoneme with t samples_per_frame <
+ *   phn_ends[b,k] (int64 [B,L], exclusive ends in samples), the last one if there is none.
+ * mlvae_center_lsm_fwd / _bwd: y = log_softmax(x - mean_t(x), dim = -1) over contiguous [B,T,C],
+ *   the mean over all T rows of the padded batch (ref:src/models/HMM_DNN_ALI/model.py:43-44), and
+ *   its backward from dy and y.  ws: mlvae_center_lsm_workspace_size bytes. */
+int mlvae_lattice_max_nodes(void);
+size_t mlvae_lattice_workspace_size(int B, int T, int L, int spp, int topology);
+int mlvae_lattice_fb(int B, int T, int C, int L, const float* pout, int ld, const float* lens,
+                     const long long* phns, const float* phn_lens, int spp, int topology, int blank,
+                     int need_beta, float* score, void* ws, size_t ws_bytes, int* err, void* stream);
+int mlvae_lattice_grad(int B, int T, int C, int L, const float* pout, int ld, const float* lens,
+                       const long long* phns, const float* phn_lens, int spp, int topology, int blank,
+                       const float* g, const void* ws, size_t ws_bytes, float* dpout, int ldd,
+                       void* stream);
+size_t mlvae_hmm_viterbi_workspace_size(int B, int T);
+int mlvae_hmm_viterbi(int B, int T, int C, int L, const float* pout, int ld, const float* lens,
+                      const long long* phns, const float* phn_lens, int spp, float* vscore, int* align,
+                      void* ws, size_t ws_bytes, int* err, void* stream);
+int mlvae_align_counts(int B, int T, int L, const int* align, const float* lens, const long long* phns,
+                       const float* phn_lens, int spp, const long long* phn_ends,
+                       long long samples_per_frame, int* counts, void* stream);
+size_t mlvae_center_lsm_workspace_size(int B, int C);
+int mlvae_center_lsm_fwd(int B, int T, int C, const float* x, float* y, void* ws, size_t ws_bytes,
+                         void* stream);
+int mlvae_center_lsm_bwd(int B, int T, int C, const float* dy, const float* y, float* dx, void* ws,
+                         size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

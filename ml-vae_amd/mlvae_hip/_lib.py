@@ -161,6 +161,17 @@ _SIGS = {
     "mlvae_norm_stats": [I, I, I, P, P, P, P, F, P],
     "mlvae_norm_update": [I, P, P, P, I, F, F, P],
     "mlvae_norm_apply": [SZ, I, P, P, P, P, P],
+    # the aligner's sequence lattice (csrc/align.hip)
+    "mlvae_lattice_max_nodes": [],
+    "mlvae_lattice_workspace_size": [I, I, I, I, I],
+    "mlvae_lattice_fb": [I, I, I, I, P, I, P, P, P, I, I, I, I, P, P, SZ, P, P],
+    "mlvae_lattice_grad": [I, I, I, I, P, I, P, P, P, I, I, I, P, P, SZ, P, I, P],
+    "mlvae_hmm_viterbi_workspace_size": [I, I],
+    "mlvae_hmm_viterbi": [I, I, I, I, P, I, P, P, P, I, P, P, P, SZ, P, P],
+    "mlvae_align_counts": [I, I, I, P, P, P, P, I, P, C.c_longlong, P, P],
+    "mlvae_center_lsm_workspace_size": [I, I],
+    "mlvae_center_lsm_fwd": [I, I, I, P, P, P, SZ, P],
+    "mlvae_center_lsm_bwd": [I, I, I, P, P, P, P, SZ, P],
 }
 _RESTYPE = {
     "mlvae_last_error": C.c_char_p,
@@ -179,6 +190,9 @@ _RESTYPE = {
     "mlvae_heads_bias_workspace_size": SZ,
     "mlvae_heads_wgrad_workspace_size": SZ,
     "mlvae_flvl_head_workspace_size": SZ,
+    "mlvae_lattice_workspace_size": SZ,
+    "mlvae_hmm_viterbi_workspace_size": SZ,
+    "mlvae_center_lsm_workspace_size": SZ,
 }
 
 _lib = None

@@ -1374,3 +1374,185 @@ def gmm_collapsed(P, eps, expo, N, Z, tau, seed):
     GmmLatentFn's sampled_h and loss with its own weights, in one launch each way."""
     _latent_shapes("gmm_collapsed", P, eps, expo, N, Z)
     return HvaeLatentFn.apply(None, P, None, None, eps, expo, N, Z, tau, seed)[2:]
+
+
+# --------------------------------------------------------------------------- HMM / CTC sequence lattice
+ALIGN_ERR_SHORT = 512    # bit of the _md_err word: HMM chain infeasible (T_i < U_i, U_i = 0 or T_i = 0)
+ALIGN_ERR_CLASS = 1024   # bit of the _md_err word: a phoneme id whose state class is outside [0, C)
+ALIGN_ERR_BLANK = 2048   # bit of the _md_err word: CTC, a target class equal to blank
+TOPO_HMM, TOPO_CTC = 0, 1
+
+
+def raise_align_err():
+    """Read the device error word's lattice bits (one host sync) and clear them alone:
+    AssertionError naming the condition (what the aligner's own asserts would have said per batch)."""
+    err = _md_err()
+    mask = ALIGN_ERR_SHORT | ALIGN_ERR_CLASS | ALIGN_ERR_BLANK
+    code = int(err.item()) & mask
+    if code:
+        err.bitwise_and_(~mask)
+        what = []
+        if code & ALIGN_ERR_SHORT:
+            what.append("an utterance has fewer frames than HMM states (or no states, or no frames)")
+        if code & ALIGN_ERR_CLASS:
+            what.append("a phoneme id expands to a state class outside [0, C)")
+        if code & ALIGN_ERR_BLANK:
+            what.append("a CTC target class equals the blank index")
+        raise AssertionError("sequence lattice: " + "; ".join(what))
+
+
+class CenterLogSoftmaxFn(torch.autograd.Function):
+    """y = log_softmax(x - mean_t(x), dim=-1) over [B, T, C], the mean over all T rows of the
+    padded batch (ref:src/models/HMM_DNN_ALI/model.py:43-44)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _need(x, "center_log_softmax x")
+        B, T, C = x.shape
+        y = torch.empty_like(x)
+        ws = _workspace(lib().mlvae_center_lsm_workspace_size(B, C), "center_lsm")
+        check(lib().mlvae_center_lsm_fwd(B, T, C, _p(x), _p(y), _p(ws), ws.numel() * 4, _stream()),
+              "center_lsm_fwd")
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        y, = ctx.saved_tensors
+        B, T, C = y.shape
+        dy = _need(dy, "center_log_softmax grad")
+        dx = torch.empty_like(y)
+        ws = _workspace(lib().mlvae_center_lsm_workspace_size(B, C), "center_lsm")
+        check(lib().mlvae_center_lsm_bwd(B, T, C, _p(dy), _p(y), _p(dx), _p(ws), ws.numel() * 4,
+                                         _stream()), "center_lsm_bwd")
+        return dx
+
+
+def center_log_softmax(x):
+    if x.dim() != 3 or x.shape[2] < 1:
+        raise ValueError(f"center_log_softmax: x must be [B, T, C] with C >= 1, got {tuple(x.shape)}")
+    return CenterLogSoftmaxFn.apply(x)
+
+
+def _lattice_args(what, pout, lens, phns, phn_lens, spp):
+    if pout.dim() != 3 or pout.shape[2] < 1:
+        raise ValueError(f"{what}: pout must be [B, T, C] with C >= 1, got {tuple(pout.shape)}")
+    if phns.dim() != 2 or phns.shape[0] != pout.shape[0]:
+        raise ValueError(f"{what}: phns must be [{pout.shape[0]}, L], got {tuple(phns.shape)}")
+    spp = int(spp)
+    if spp < 1:
+        raise ValueError(f"{what}: states per phoneme must be >= 1, got {spp}")
+    B, L = phns.shape
+    fl = _score_lens(lens, B, pout.device, f"{what} frame")
+    pl = _score_lens(phn_lens, B, pout.device, f"{what} phoneme")
+    ids = phns.to(pout.device, torch.int64).contiguous()
+    return fl, pl, ids, L, spp
+
+
+class LatticeFn(torch.autograd.Function):
+    """score [B] = log of the summed path likelihoods of the HMM or CTC chain (csrc/align.hip).
+    The forward runs the alpha chain (and, when a gradient is wanted, the beta chain beside it);
+    the backward is the occupancy pass with g = the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, pout, fl, ids, pl, spp, topo, blank):
+        pout = _need(pout, "lattice pout")
+        B, T, C = pout.shape
+        L = ids.shape[1]
+        limit = lib().mlvae_lattice_max_nodes()
+        nodes = L * spp * (2 if topo == TOPO_CTC else 1) + (1 if topo == TOPO_CTC else 0)
+        if nodes > limit:
+            raise ValueError(f"lattice: {L} phonemes of {spp} states give a chain of {nodes} nodes, "
+                             f"the kernel holds at most {limit}")
+        need_beta = bool(ctx.needs_input_grad[0])
+        nbytes = lib().mlvae_lattice_workspace_size(B, T, L, spp, topo)
+        ws = torch.empty(max(nbytes // 4, 1), device=pout.device, dtype=torch.float32)
+        score = torch.empty(B, device=pout.device, dtype=torch.float32)
+        check(lib().mlvae_lattice_fb(B, T, C, L, _p(pout), C, _p(fl), ids.data_ptr(), _p(pl), spp, topo,
+                                     blank, int(need_beta), _p(score), _p(ws), ws.numel() * 4,
+                                     _p(_md_err()), _stream()), "lattice_fb")
+        if need_beta:
+            ctx.save_for_backward(pout, fl, ids, pl, ws)
+        ctx.cfg = (spp, topo, blank)
+        return score
+
+    @staticmethod
+    def backward(ctx, g):
+        pout, fl, ids, pl, ws = ctx.saved_tensors
+        spp, topo, blank = ctx.cfg
+        B, T, C = pout.shape
+        g = _need(g, "lattice grad")
+        dpout = torch.empty_like(pout)
+        check(lib().mlvae_lattice_grad(B, T, C, ids.shape[1], _p(pout), C, _p(fl), ids.data_ptr(), _p(pl),
+                                       spp, topo, blank, _p(g), _p(ws), ws.numel() * 4, _p(dpout), C,
+                                       _stream()), "lattice_grad")
+        return dpout, None, None, None, None, None, None
+
+
+def hmm_forward(pout, lens, phns, phn_lens, spp):
+    """score [B]: log sum over the left-to-right HMM paths of exp(sum_t pout[b, t, state_t]) --
+    the forward score SpeechBrain's HMMAligner trains on.  pout [B, T, C] log-probabilities, phns
+    [B, L] phoneme ids (each expands into spp states of classes id * spp + j), lens / phn_lens the
+    relative lengths.  Autograd: d score_b / d pout = the state occupancies.  An infeasible
+    utterance or a bad id scores 0 and sets a bit of the device error word (raise_align_err)."""
+    fl, pl, ids, _, spp = _lattice_args("hmm_forward", pout, lens, phns, phn_lens, spp)
+    return LatticeFn.apply(pout, fl, ids, pl, spp, TOPO_HMM, 0)
+
+
+def ctc_nll(pout, lens, phns, phn_lens, spp, blank):
+    """nll [B] = -log p(targets | pout) of the CTC chain over the spp-expanded phonemes:
+    F.ctc_loss(reduction='none', zero_infinity=True) per utterance, on log-probabilities pout.
+    The gradient is the true partial derivative with respect to pout (minus the occupancies), not
+    torch's, which folds the log-softmax backward in: chained through a log-softmax both agree."""
+    fl, pl, ids, _, spp = _lattice_args("ctc_nll", pout, lens, phns, phn_lens, spp)
+    blank = int(blank)
+    if not 0 <= blank < pout.shape[2]:
+        raise ValueError(f"ctc_nll: blank {blank} outside [0, {pout.shape[2]})")
+    return -LatticeFn.apply(pout, fl, ids, pl, spp, TOPO_CTC, blank)
+
+
+def hmm_viterbi(pout, lens, phns, phn_lens, spp):
+    """(vscore [B] fp32, align [B, T] int32): the best HMM path's score (float64 sums, rounded
+    once) and its state position per frame in [0, U_i), -1 past T_i; a tie keeps "stay".  No
+    gradient; errors as hmm_forward's."""
+    fl, pl, ids, L, spp = _lattice_args("hmm_viterbi", pout, lens, phns, phn_lens, spp)
+    pout = _need(pout.detach(), "hmm_viterbi pout")
+    B, T, C = pout.shape
+    limit = lib().mlvae_lattice_max_nodes()
+    if L * spp > limit:
+        raise ValueError(f"hmm_viterbi: {L} phonemes of {spp} states, the kernel holds at most {limit} states")
+    ws = _workspace(lib().mlvae_hmm_viterbi_workspace_size(B, T), "hmm_viterbi")
+    vscore = torch.empty(B, device=pout.device, dtype=torch.float32)
+    align = torch.empty(B, T, device=pout.device, dtype=torch.int32)
+    check(lib().mlvae_hmm_viterbi(B, T, C, L, _p(pout), C, _p(fl), ids.data_ptr(), _p(pl), spp,
+                                  _p(vscore), align.data_ptr(), _p(ws), ws.numel() * 4, _p(_md_err()),
+                                  _stream()), "hmm_viterbi")
+    return vscore, align
+
+
+def align_counts(align, lens, phns, phn_lens, spp, phn_ends, samples_per_frame):
+    """int32 [B, 2] = (frames correct, T_i) per utterance of a Viterbi alignment (int32 [B, T] state
+    positions): frame t is correct iff the phoneme of its state, phns[i, align[i, t] // spp], is
+    the phoneme of the ground-truth segment that holds it -- the first k with t * samples_per_frame
+    < phn_ends[i, k] (exclusive ends in samples), the last phoneme if none.  What
+    AlignAccMetricStats.append_counts takes; stays on the device."""
+    if align.dim() != 2 or align.dtype != torch.int32 or not align.is_cuda:
+        raise TypeError(f"align_counts: align must be an int32 [B, T] HIP tensor, got {align.dtype} "
+                        f"{tuple(align.shape)} on {align.device}")
+    align = align.contiguous()
+    B, T = align.shape
+    if phns.dim() != 2 or phns.shape[0] != B or tuple(phn_ends.shape) != tuple(phns.shape):
+        raise ValueError(f"align_counts: phns and phn_ends must be [{B}, L], got {tuple(phns.shape)} "
+                         f"and {tuple(phn_ends.shape)}")
+    spp, spf = int(spp), int(samples_per_frame)
+    if spp < 1 or spf < 1:
+        raise ValueError(f"align_counts: spp {spp} and samples_per_frame {spf} must be >= 1")
+    L = phns.shape[1]
+    fl = _score_lens(lens, B, align.device, "align_counts frame")
+    pl = _score_lens(phn_lens, B, align.device, "align_counts phoneme")
+    ids = phns.to(align.device, torch.int64).contiguous()
+    ends = phn_ends.to(align.device, torch.int64).contiguous()
+    counts = torch.zeros(B, 2, device=align.device, dtype=torch.int32)
+    check(lib().mlvae_align_counts(B, T, L, align.data_ptr(), _p(fl), ids.data_ptr(), _p(pl), spp,
+                                   ends.data_ptr(), spf, counts.data_ptr(), _stream()), "align_counts")
+    return counts

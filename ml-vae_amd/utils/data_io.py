@@ -12,7 +12,9 @@
   and flvl_gt_md_lbl_seq (the LSTM_FC baseline's frame-level targets), derived from them.
   ``phn_labels=True`` (``synthetic.phn_labels``) with it adds flvl_gt_cnncl_seq, the canonical
   phoneme id of every frame (test_phn_classifier's frame-level targets), derived likewise: it
-  takes no draw, so every other field is the same with and without it.
+  takes no draw, so every other field is the same with and without it.  ``ali_labels=True``
+  (``synthetic.ali_labels``) with md_labels adds gt_phn_end_seq, the exclusive end of every
+  gt_boundary_seq segment in samples (the HMM_DNN_ALI aligner's ground truth), derived too.
 
 Batches follow SpeechBrain's PaddedBatch: batch['feat'] = (padded [B, Tmax, F], relative lengths
 [B]).  Under data parallelism rank r of W reads utterances [r*bs, (r+1)*bs) of every global batch
@@ -246,9 +248,19 @@ def _synthetic_md_labels(T, n_phonemes, g, phn_labels=False):
     return out
 
 
+def _phn_end_seq(gt_boundary_seq, samples_per_frame):
+    """Exclusive end of every gt_boundary_seq segment, in samples (int64 [L]): derived, no draw."""
+    starts = torch.where(gt_boundary_seq == 1)[0]
+    ends = torch.cat([starts[1:], starts.new_tensor([gt_boundary_seq.shape[0]])])
+    return ends.to(torch.int64) * int(samples_per_frame)
+
+
 class SyntheticSet:
     def __init__(self, n_utts, feat_dim, min_frames, max_frames, seed, sorting="descending",
-                 md_labels=False, n_phonemes=39, phn_labels=False):
+                 md_labels=False, n_phonemes=39, phn_labels=False, ali_labels=False,
+                 samples_per_frame=320):
+        if ali_labels and not md_labels:
+            raise ValueError("synthetic corpus: ali_labels needs md_labels")
         g = torch.Generator().manual_seed(seed)
         lens = torch.randint(min_frames, max_frames + 1, (n_utts,), generator=g)
         self.items = []
@@ -263,6 +275,8 @@ class SyntheticSet:
                 e.update(_synthetic_md_labels(e["feat"].shape[0], n_phonemes, _label_generator(seed, i),
                                               phn_labels=phn_labels))
                 e["prior"] = prior.clone()
+                if ali_labels:
+                    e["gt_phn_end_seq"] = _phn_end_seq(e["gt_boundary_seq"], samples_per_frame)
         _sort(self.items, sorting)
         self.sorting = sorting
 
@@ -297,5 +311,8 @@ def prepare_datasets(hparams):
                                  hparams.get("sorting", "descending"),
                                  md_labels=bool(d.get("md_labels", False)),
                                  n_phonemes=int(hparams.get("n_phonemes", 39)),
-                                 phn_labels=bool(d.get("phn_labels", False))))
+                                 phn_labels=bool(d.get("phn_labels", False)),
+                                 ali_labels=bool(d.get("ali_labels", False)),
+                                 samples_per_frame=int(hparams.get("sample_rate", 16000)) *
+                                 int(hparams.get("hop_length", 20)) // 1000))
     return sets, None
