@@ -877,6 +877,37 @@ int mlvae_center_lsm_fwd(int B, int T, int C, const float* x, float* y, void* ws
 int mlvae_center_lsm_bwd(int B, int T, int C, const float* dy, const float* y, float* dx, void* ws,
                          size_t ws_bytes, void* stream);
 
+/* The feature front end (csrc/fbank.hip): waveform -> log-mel filterbank, deltas, delta-deltas, the
+ * reference's compute_features = speechbrain.lobes.features.Fbank(deltas=True, context=False)
+ * (ref:src/config/run.yaml:39-44, applied per utterance at ref:src/utils/data_io.py:187-214),
+ * restated from SpeechBrain 0.5 (parity unpinned; the pin is tests/fbank_ref.py in float64).
+ * wav [B, Nmax] fp32 (row stride ld), n_samples [B] int32 on the device (clamped to [0, Nmax]);
+ * hop, win, n_fft in samples.  Per utterance: T_b = 1 + N_b / hop frames; frame t covers samples
+ * [t hop - n_fft/2, t hop + n_fft/2), zero outside [0, N_b) (nothing at or past N_b is read: the
+ * padding may hold anything); periodic Hamming window of win points centred in n_fft; |X_k|^2 for
+ * k = 0 .. n_fft/2; n_mels triangular filters on the HTK mel scale over [f_min, f_max];
+ * 10 log10(max(mel, 1e-10)) clamped from below at (the utterance's own maximum) - 80;
+ * delta_t = sum_{k=-2..2} k x_{clamp(t+k, 0, T_b-1)} / 10, applied twice.
+ * out [B, Tmax, 3 n_mels] (row stride ldo, Tmax = 1 + Nmax / hop) = (static | delta | delta-delta),
+ * rows t >= T_b exact zeros; frames [B] int32 = T_b.  N_b = 0 is one frame of -100 dB statics.
+ * fp32 operands and accumulation (exact-f32 MFMA); no floating-point atomics and tiles are per
+ * utterance: a rerun is bit-identical and an utterance's rows do not depend on the rest of the batch.
+ * Limits (status 1): n_fft even and <= 512, 1 <= win <= n_fft, 1 <= n_mels <= 64, hop >= 1,
+ * B <= 65535.  B == 0 is a no-op.
+ * mlvae_fbank_table fills a HOST buffer of mlvae_fbank_table_size(win, n_fft, n_mels) bytes with the
+ * windowed twiddles and the filter weights (computed in float64, rounded to fp32); the caller
+ * uploads it once per geometry and passes the device copy as `table` (the library allocates
+ * nothing).  ws: mlvae_fbank_workspace_size(B, Nmax, hop, n_mels) bytes (the unclamped dB frames
+ * and one maximum per 32-frame tile).  The size functions return 0 for a geometry outside the
+ * limits (mlvae_last_error says why). */
+size_t mlvae_fbank_table_size(int win, int n_fft, int n_mels);
+size_t mlvae_fbank_workspace_size(int B, int Nmax, int hop, int n_mels);
+int mlvae_fbank_table(int sample_rate, int win, int n_fft, int n_mels, float f_min, float f_max,
+                      float* host_table, size_t table_bytes);
+int mlvae_fbank(int B, int Nmax, const float* wav, int ld, const int* n_samples, int hop, int win,
+                int n_fft, int n_mels, const float* table, float* out, int ldo, int* frames, void* ws,
+                size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,10 @@ SpeechBrain 0.5 semantics restated (parity unpinned): per-utterance mean/std ove
 round(len*T) frames, averaged over the batch; in train mode the global statistics are set on
 the first batch and then running-averaged with weight 1/(count+1) while
 epoch < update_until_epoch; x <- (x - mean) / std.  Device-side torch ops with no host
-synchronisation (outside the fused train step, which takes already normalised features)."""
+synchronisation (outside the fused train step, which takes already normalised features).
+
+Fbank: the reference's compute_features (ref:src/config/run.yaml:39-44), waveform -> log-mel
+filterbank + deltas + delta-deltas on the HIP kernels of csrc/fbank.hip."""
 import torch
 
 
@@ -68,3 +71,46 @@ class InputNormalization(torch.nn.Module):
         if self.std_norm:
             out = out / self.glob_std
         return out
+
+
+class Fbank(torch.nn.Module):
+    """speechbrain.lobes.features.Fbank as the reference configures it (compute_features,
+    ref:src/config/run.yaml:39-44; applied per utterance at ref:src/utils/data_io.py:187-214):
+    waveform [B, N] -> log-mel filterbank [B, T, n_mels], with deltas and delta-deltas
+    [B, T, 3 n_mels] (static | delta | delta-delta), T = 1 + N // hop.  SpeechBrain 0.5's
+    constructor names and semantics restated (parity unpinned, include/mlvae.h mlvae_fbank); the
+    work is two HIP kernels (mlvae_hip.ops.fbank), per utterance: with wav_lens (relative,
+    N_b = round(N len_b)) an utterance's frames, its 80 dB floor and its delta edges are those of
+    the unpadded waveform, and the rows past 1 + N_b // hop are zeros.  hop_length / win_length in
+    milliseconds.  Constructing it touches neither the device nor a random generator."""
+
+    def __init__(self, deltas=False, context=False, requires_grad=False, sample_rate=16000, f_min=0,
+                 f_max=None, n_fft=400, n_mels=40, filter_shape="triangular", left_frames=5,
+                 right_frames=5, win_length=25, hop_length=10):
+        super().__init__()
+        if context:
+            raise NotImplementedError("Fbank(context=True): context windows are not built (no recipe "
+                                      "of the reference uses them)")
+        if requires_grad:
+            raise NotImplementedError("Fbank(requires_grad=True): the filterbank is a fixed table of "
+                                      "the kernels; learnable filters need a backward that is not built")
+        if filter_shape != "triangular":
+            raise NotImplementedError(f"Fbank(filter_shape={filter_shape!r}): the kernels' filter table "
+                                      "holds triangular filters only")
+        self.deltas, self.context = bool(deltas), False
+        self.sample_rate, self.n_fft, self.n_mels = int(sample_rate), int(n_fft), int(n_mels)
+        self.f_min = float(f_min)
+        self.f_max = float(sample_rate / 2 if f_max is None else f_max)
+        self.filter_shape = filter_shape
+        self.left_frames, self.right_frames = left_frames, right_frames
+        self.win_length, self.hop_length = win_length, hop_length
+
+    @torch.no_grad()
+    def forward(self, wav, wav_lens=None):
+        from mlvae_hip import ops
+        if wav_lens is not None:
+            wav_lens = torch.as_tensor(wav_lens, dtype=torch.float32)
+        feats, _ = ops.fbank(wav, wav_lens, sample_rate=self.sample_rate, hop_length=self.hop_length,
+                             win_length=self.win_length, n_fft=self.n_fft, n_mels=self.n_mels,
+                             f_min=self.f_min, f_max=self.f_max)
+        return feats if self.deltas else feats[..., :self.n_mels]

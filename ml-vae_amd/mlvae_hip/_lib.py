@@ -172,6 +172,11 @@ _SIGS = {
     "mlvae_center_lsm_workspace_size": [I, I],
     "mlvae_center_lsm_fwd": [I, I, I, P, P, P, SZ, P],
     "mlvae_center_lsm_bwd": [I, I, I, P, P, P, P, SZ, P],
+    # the feature front end (csrc/fbank.hip)
+    "mlvae_fbank_table_size": [I, I, I],
+    "mlvae_fbank_workspace_size": [I, I, I, I],
+    "mlvae_fbank_table": [I, I, I, I, F, F, P, SZ],
+    "mlvae_fbank": [I, I, P, I, P, I, I, I, I, P, P, I, P, P, SZ, P],
 }
 _RESTYPE = {
     "mlvae_last_error": C.c_char_p,
@@ -193,6 +198,8 @@ _RESTYPE = {
     "mlvae_lattice_workspace_size": SZ,
     "mlvae_hmm_viterbi_workspace_size": SZ,
     "mlvae_center_lsm_workspace_size": SZ,
+    "mlvae_fbank_table_size": SZ,
+    "mlvae_fbank_workspace_size": SZ,
 }
 
 _lib = None

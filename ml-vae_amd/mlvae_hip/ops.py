@@ -1556,3 +1556,67 @@ def align_counts(align, lens, phns, phn_lens, spp, phn_ends, samples_per_frame):
     check(lib().mlvae_align_counts(B, T, L, align.data_ptr(), _p(fl), ids.data_ptr(), _p(pl), spp,
                                    ends.data_ptr(), spf, counts.data_ptr(), _stream()), "align_counts")
     return counts
+
+
+# ---- the feature front end (csrc/fbank.hip)
+_fbank_tables = {}
+
+
+def _fbank_table(dev, sample_rate, win, n_fft, n_mels, f_min, f_max):
+    """The windowed twiddles and mel filters of one geometry on one device: filled once on the host
+    (mlvae_fbank_table, float64 rounded to fp32) and kept."""
+    key = (dev, sample_rate, win, n_fft, n_mels, float(f_min), float(f_max))
+    t = _fbank_tables.get(key)
+    if t is None:
+        nbytes = lib().mlvae_fbank_table_size(win, n_fft, n_mels)
+        if nbytes == 0:
+            check(1, "fbank")
+        host = torch.empty(nbytes // 4, dtype=torch.float32)
+        check(lib().mlvae_fbank_table(sample_rate, win, n_fft, n_mels, float(f_min), float(f_max),
+                                      host.data_ptr(), nbytes), "fbank_table")
+        t = _fbank_tables[key] = host.to(dev)
+    return t
+
+
+def fbank(wav, wav_lens=None, *, sample_rate=16000, hop_length=10, win_length=25, n_fft=400, n_mels=40,
+          f_min=0.0, f_max=None):
+    """(feats [B, Tmax, 3 n_mels] fp32, frames [B] int32) of the padded waveforms wav [B, N]:
+    log-mel filterbank, deltas and delta-deltas as SpeechBrain's Fbank(deltas=True) computes them
+    per utterance (include/mlvae.h, mlvae_fbank), Tmax = 1 + N // hop, rows past an utterance's
+    frames[b] = 1 + N_b // hop exact zeros.  wav_lens: None (every row N samples), an integer
+    tensor of sample counts N_b, or a floating tensor of relative lengths (N_b = round(N len_b));
+    samples at or past N_b are never read.  hop_length / win_length in milliseconds.  No autograd:
+    the front end has no parameters; an input that requires grad raises."""
+    if wav.dim() != 2:
+        raise ValueError(f"fbank: wav must be [B, N], got {tuple(wav.shape)}")
+    if wav.requires_grad:
+        raise RuntimeError("fbank: the front end has no backward; detach the waveform")
+    wav = _need(wav, "fbank wav")
+    B, N = wav.shape
+    dev = wav.device
+    sample_rate, n_fft, n_mels = int(sample_rate), int(n_fft), int(n_mels)
+    # samples from SpeechBrain's milliseconds
+    hop, win = (int(round(sample_rate / 1000.0 * ms)) for ms in (hop_length, win_length))
+    f_max = sample_rate / 2 if f_max is None else f_max
+    if wav_lens is None:
+        ns = torch.full((B,), N, device=dev, dtype=torch.int32)
+    else:
+        wav_lens = torch.as_tensor(wav_lens)
+        if tuple(wav_lens.shape) != (B,):
+            raise ValueError(f"fbank: wav_lens must be [{B}], got {tuple(wav_lens.shape)}")
+        if wav_lens.is_floating_point():
+            ns = torch.round(wav_lens.to(dev, torch.float64) * N).to(torch.int32)
+        else:
+            ns = wav_lens.to(dev, torch.int32)
+        ns = ns.contiguous()
+    # geometry errors come from the library (status 1 with its message)
+    table = _fbank_table(dev, sample_rate, win, n_fft, n_mels, f_min, f_max)
+    Tmax = 1 + N // max(hop, 1)
+    feats = torch.empty(B, Tmax, 3 * n_mels, device=dev, dtype=torch.float32)
+    frames = torch.empty(B, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        ws = _workspace(lib().mlvae_fbank_workspace_size(B, N, hop, n_mels), "fbank")
+        check(lib().mlvae_fbank(B, N, _p(wav) if N else None, N, ns.data_ptr(), hop, win, n_fft, n_mels,
+                                _p(table), _p(feats), 3 * n_mels, frames.data_ptr(), _p(ws),
+                                ws.numel() * 4, _stream()), "fbank")
+    return feats, frames

@@ -15,6 +15,9 @@
   takes no draw, so every other field is the same with and without it.  ``ali_labels=True``
   (``synthetic.ali_labels``) with md_labels adds gt_phn_end_seq, the exclusive end of every
   gt_boundary_seq segment in samples (the HMM_DNN_ALI aligner's ground truth), derived too.
+  ``waveforms=True`` (``synthetic.waveforms``) with md_labels makes the corpus spoken: wav and
+  gt_phn_seq from a third generator per utterance, feat = compute_features(wav) (the Fbank front
+  end, brain.features.Fbank) -- see SyntheticSet.
 
 Batches follow SpeechBrain's PaddedBatch: batch['feat'] = (padded [B, Tmax, F], relative lengths
 [B]).  Under data parallelism rank r of W reads utterances [r*bs, (r+1)*bs) of every global batch
@@ -255,12 +258,91 @@ def _phn_end_seq(gt_boundary_seq, samples_per_frame):
     return ends.to(torch.int64) * int(samples_per_frame)
 
 
+F1_HZ = (300, 420, 560, 720, 900, 1100)                 # first tone of a spoken phoneme: id % 6
+F2_HZ = (1400, 1700, 2050, 2450, 2900, 3400, 4000)      # second tone: (id // 6) % 7
+MAX_SPOKEN_PHONEMES = len(F1_HZ) * len(F2_HZ)           # 42 distinct tone pairs
+WAV_NOISE = 0.01                                        # white noise floor of the waveform
+WAV_BATCH = 16                                          # utterances per front-end call
+
+
+def _wave_generator(seed, index):
+    """The waveform stream of one utterance (pronounced ids, phases, noise): its own generator,
+    as _label_generator, so neither the features' nor the labels' draws move."""
+    return torch.Generator().manual_seed((int(seed) * 1000003 + index + 1) % (2 ** 63 - 1) + 0x5756)
+
+
+def _spoken_utterance(e, n_phonemes, samples_per_frame, sample_rate, g):
+    """(gt_phn_seq int64 [L], wav float32 [T samples_per_frame]) of one labelled utterance: the
+    pronounced id is the canonical one where plvl_gt_md_lbl_seq is 0 and another one where it is
+    1; every gt_boundary_seq segment sounds the two tones of its pronounced id."""
+    cnncl, plvl, gt = e["gt_cnncl_seq"], e["plvl_gt_md_lbl_seq"], e["gt_boundary_seq"]
+    L, T = cnncl.shape[0], gt.shape[0]
+    other = (cnncl + 1 + torch.randint(0, n_phonemes - 1, (L,), generator=g)) % n_phonemes
+    phn = torch.where(plvl == 1, other, cnncl)
+    ends = _phn_end_seq(gt, samples_per_frame).tolist()
+    phase = 2 * np.pi * torch.rand(L, 2, generator=g, dtype=torch.float64).numpy()
+    n = np.arange(T * samples_per_frame, dtype=np.float64)
+    wav = np.empty_like(n)
+    lo = 0
+    for k, hi in enumerate(ends):
+        p = int(phn[k])
+        w1 = 2 * np.pi * F1_HZ[p % len(F1_HZ)] / sample_rate
+        w2 = 2 * np.pi * F2_HZ[(p // len(F1_HZ)) % len(F2_HZ)] / sample_rate
+        wav[lo:hi] = 0.5 * np.sin(w1 * n[lo:hi] + phase[k, 0]) + 0.3 * np.sin(w2 * n[lo:hi] + phase[k, 1])
+        lo = hi
+    noise = torch.randn(T * samples_per_frame, generator=g, dtype=torch.float64).numpy()
+    return phn, torch.from_numpy((wav + WAV_NOISE * noise).astype(np.float32))
+
+
+def _spoken_features(items, compute_features, feat_dim):
+    """feat = compute_features(wav) of every utterance, in padded batches of WAV_BATCH, trimmed to
+    the labels' T frames (the front end yields T + 1; ref:src/utils/data_io.py:199-201 trims the
+    same way), kept on the host as the random features are."""
+    dev = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
+    for i in range(0, len(items), WAV_BATCH):
+        part = items[i:i + WAV_BATCH]
+        N = max(e["wav"].shape[0] for e in part)
+        wav = torch.zeros(len(part), N)
+        for j, e in enumerate(part):
+            wav[j, :e["wav"].shape[0]] = e["wav"]
+        lens = torch.tensor([e["wav"].shape[0] / N for e in part], dtype=torch.float32)
+        feats = torch.as_tensor(compute_features(wav.to(dev), lens.to(dev))).detach().cpu().float()
+        for j, e in enumerate(part):
+            T = e["feat"].shape[0]
+            if feats.dim() != 3 or feats.shape[1] < T:
+                raise ValueError(f"synthetic corpus: compute_features gave {tuple(feats.shape)} for "
+                                 f"an utterance of {T} frames")
+            if feats.shape[2] != feat_dim:
+                raise ValueError(f"synthetic corpus: compute_features gives {feats.shape[2]}-d frames, "
+                                 f"the model's input_size is {feat_dim}")
+            e["feat"] = feats[j, :T].clone()
+
+
 class SyntheticSet:
+    """waveforms=True (``synthetic.waveforms``, with md_labels) makes the corpus *spoken*: every
+    utterance gets gt_phn_seq (the pronounced ids: canonical where plvl_gt_md_lbl_seq is 0,
+    another id where it is 1) and wav (T samples_per_frame float32 samples: two tones per
+    pronounced phoneme over its gt_boundary_seq segment plus a noise floor), and feat becomes
+    compute_features(wav) -- so the features carry the labels.  Every other field keeps the value
+    it has without waveforms: the feature generator still takes its draws and the new fields come
+    from a generator of their own per utterance.  Under data parallelism every rank builds the
+    same corpus (nothing here depends on the rank) and reads its slice of each batch."""
+
     def __init__(self, n_utts, feat_dim, min_frames, max_frames, seed, sorting="descending",
                  md_labels=False, n_phonemes=39, phn_labels=False, ali_labels=False,
-                 samples_per_frame=320):
+                 samples_per_frame=320, waveforms=False, compute_features=None, sample_rate=16000):
         if ali_labels and not md_labels:
             raise ValueError("synthetic corpus: ali_labels needs md_labels")
+        if waveforms:
+            if not md_labels:
+                raise ValueError("synthetic corpus: waveforms needs md_labels (the waveform is "
+                                 "synthesised from the phoneme and boundary labels)")
+            if not 2 <= n_phonemes <= MAX_SPOKEN_PHONEMES:
+                raise ValueError(f"synthetic corpus: waveforms has {MAX_SPOKEN_PHONEMES} distinct tone "
+                                 f"pairs, n_phonemes = {n_phonemes} must be in [2, {MAX_SPOKEN_PHONEMES}]")
+            if compute_features is None:
+                raise ValueError("synthetic corpus: waveforms needs compute_features (config/run.yaml's "
+                                 "compute_features: the Fbank front end)")
         g = torch.Generator().manual_seed(seed)
         lens = torch.randint(min_frames, max_frames + 1, (n_utts,), generator=g)
         self.items = []
@@ -277,6 +359,11 @@ class SyntheticSet:
                 e["prior"] = prior.clone()
                 if ali_labels:
                     e["gt_phn_end_seq"] = _phn_end_seq(e["gt_boundary_seq"], samples_per_frame)
+        if waveforms:
+            for i, e in enumerate(self.items):
+                e["gt_phn_seq"], e["wav"] = _spoken_utterance(e, n_phonemes, int(samples_per_frame),
+                                                              int(sample_rate), _wave_generator(seed, i))
+            _spoken_features(self.items, compute_features, feat_dim)
         _sort(self.items, sorting)
         self.sorting = sorting
 
@@ -314,5 +401,8 @@ def prepare_datasets(hparams):
                                  phn_labels=bool(d.get("phn_labels", False)),
                                  ali_labels=bool(d.get("ali_labels", False)),
                                  samples_per_frame=int(hparams.get("sample_rate", 16000)) *
-                                 int(hparams.get("hop_length", 20)) // 1000))
+                                 int(hparams.get("hop_length", 20)) // 1000,
+                                 waveforms=bool(d.get("waveforms", False)),
+                                 compute_features=hparams.get("compute_features"),
+                                 sample_rate=int(hparams.get("sample_rate", 16000))))
     return sets, None
