@@ -877,6 +877,54 @@ int mlvae_center_lsm_fwd(int B, int T, int C, const float* x, float* y, void* ws
 int mlvae_center_lsm_bwd(int B, int T, int C, const float* dy, const float* y, float* dx, void* ws,
                          size_t ws_bytes, void* stream);
 
+/* The CTC evaluation kernels of the CRDNN_CTC recipes (csrc/ctc_eval.hip; ref:src/models/CRDNN_CTC/
+ * model.py:60-176).  One wave per utterance; integers, or float64 sums of the fp32 emissions in
+ * frame order; no atomics but the OR into *err: a rerun is bit-identical and tests/ctc_np.py
+ * reproduces every output bit for bit.  Lengths as the lattice's: T_b = rintf(T lens[b]) and so on.
+ * mlvae_ctc_greedy_decode: per frame t < T_b the argmax over the C classes of pout [B,T,C] (row
+ *   stride ld; a tie keeps the lowest class); frame t is kept iff its class is not blank and differs
+ *   from frame t - 1's.  pred [B,T] int32 = the kept classes in frame order, -1 behind them;
+ *   pred_len [B] int32.
+ * mlvae_edit_align: refs [B,2,L] int64 (the pronounced and the canonical phonemes), ref_lens [B,2]
+ *   relative lengths, hypothesis pred[b, :pred_len[b]] (row stride Tp).  Levenshtein with unit costs;
+ *   at cell (i, j) the diagonal only if its cost is strictly below both others, else the deletion
+ *   (from (i - 1, j)) if strictly below the insertion, else the insertion; row 0 is insertions,
+ *   column 0 deletions; the backtrace starts at (L_a, L_b).  ali [B,2,L] int32 = the hypothesis token
+ *   aligned to every reference position, -1 for a deletion and past L_a (insertions are dropped);
+ *   ops [B,2,4] int32 = (insertions, deletions, substitutions, L_a).  ws:
+ *   mlvae_edit_align_workspace_size(B, L, Tp) bytes (two bits per cell).  L above
+ *   mlvae_edit_align_max_ref() (1024): status 1.
+ * mlvae_ctc_md_counts: counts [B,8] int32 over the alignment to the pronounced sequence, with
+ *   pred_md = (ali != canonical) (a deletion counts as mispronounced) and gt_md = (pronounced !=
+ *   canonical): (both correct, both mispronounced, missed, false alarm, canonical positions, of
+ *   them recognised wrongly, mispronounced positions, of them recognised wrongly).  *err bit 4096:
+ *   the two references of an utterance differ in length (the shorter is counted).
+ * mlvae_ctc_viterbi: the best path of the CTC chain over phns [B,L] (blank, p_0, blank, .., blank;
+ *   stay / next / skip over a blank between two different classes; start in node 0 or 1, end in one
+ *   of the last two).  float64 delta; a tie keeps stay, then next, then skip; of the two end nodes a
+ *   tie keeps the final blank.  vscore [B] = the path's score rounded once; boundary [B,T] int32 = 1
+ *   at frame 0 and at the first frame of phoneme k = 1 .. L_b - 1 (exactly L_b ones), 0 at the other
+ *   frames t < T_b, -1 past T_b.  A chain without a path (T_b too short, or T_b = 0) is no error:
+ *   vscore 0, infeasible[b] = 1, ones at frames 0 .. min(L_b, T_b) - 1.  *err bits 1024 / 2048 as the
+ *   lattice's (then vscore 0, boundary -1, infeasible 0).  2 L + 1 above 1024 nodes: status 1.  ws:
+ *   mlvae_ctc_viterbi_workspace_size(B, T) bytes (two backpointer bits per node and frame).
+ * mlvae_log_softmax_fwd / _bwd: y = log_softmax(x) over the C columns of `rows` contiguous rows, and
+ *   dx = dy - exp(y) sum_c dy. */
+int mlvae_ctc_greedy_decode(int B, int T, int C, const float* pout, int ld, const float* lens, int blank,
+                            int* pred, int* pred_len, void* stream);
+int mlvae_edit_align_max_ref(void);
+size_t mlvae_edit_align_workspace_size(int B, int L, int Tp);
+int mlvae_edit_align(int B, int L, int Tp, const long long* refs, const float* ref_lens, const int* pred,
+                     const int* pred_len, int* ali, int* ops, void* ws, size_t ws_bytes, void* stream);
+int mlvae_ctc_md_counts(int B, int L, const long long* refs, const float* ref_lens, const int* ali,
+                        int* counts, int* err, void* stream);
+size_t mlvae_ctc_viterbi_workspace_size(int B, int T);
+int mlvae_ctc_viterbi(int B, int T, int C, int L, const float* pout, int ld, const float* lens,
+                      const long long* phns, const float* phn_lens, int blank, float* vscore,
+                      int* boundary, int* infeasible, void* ws, size_t ws_bytes, int* err, void* stream);
+int mlvae_log_softmax_fwd(int rows, int C, const float* x, float* y, void* stream);
+int mlvae_log_softmax_bwd(int rows, int C, const float* dy, const float* y, float* dx, void* stream);
+
 /* The feature front end (csrc/fbank.hip): waveform -> log-mel filterbank, deltas, delta-deltas, the
  * reference's compute_features = speechbrain.lobes.features.Fbank(deltas=True, context=False)
  * (ref:src/config/run.yaml:39-44, applied per utterance at ref:src/utils/data_io.py:187-214),

@@ -27,6 +27,20 @@ class InputNormalization(torch.nn.Module):
         self.register_buffer("glob_mean", torch.zeros(0))
         self.register_buffer("glob_std", torch.zeros(0))
 
+    def _load_from_state_dict(self, state_dict, prefix, *args):
+        # the statistics take their shape from the first batch: a checkpoint of a normaliser that
+        # has seen data loads into a fresh one (CRDNN_CTC applies and checkpoints its normaliser).
+        # The batch count is not part of the state: loaded statistics count as one batch, so the
+        # next training batch averages into them instead of replacing them.
+        for name in ("glob_mean", "glob_std"):
+            v = state_dict.get(prefix + name)
+            cur = getattr(self, name)
+            if v is not None and v.shape != cur.shape:
+                setattr(self, name, torch.zeros(v.shape, dtype=cur.dtype, device=cur.device))
+                if v.numel():
+                    self.count = max(self.count, 1)
+        super()._load_from_state_dict(state_dict, prefix, *args)
+
     @torch.no_grad()
     def forward(self, x, lengths, spk_ids=None, epoch=0):
         # per-utterance statistics over the first round(len*T) frames, as one masked device

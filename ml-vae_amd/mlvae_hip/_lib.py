@@ -172,6 +172,16 @@ _SIGS = {
     "mlvae_center_lsm_workspace_size": [I, I],
     "mlvae_center_lsm_fwd": [I, I, I, P, P, P, SZ, P],
     "mlvae_center_lsm_bwd": [I, I, I, P, P, P, P, SZ, P],
+    # the CTC evaluation kernels (csrc/ctc_eval.hip)
+    "mlvae_ctc_greedy_decode": [I, I, I, P, I, P, I, P, P, P],
+    "mlvae_edit_align_max_ref": [],
+    "mlvae_edit_align_workspace_size": [I, I, I],
+    "mlvae_edit_align": [I, I, I, P, P, P, P, P, P, P, SZ, P],
+    "mlvae_ctc_md_counts": [I, I, P, P, P, P, P, P],
+    "mlvae_ctc_viterbi_workspace_size": [I, I],
+    "mlvae_ctc_viterbi": [I, I, I, I, P, I, P, P, P, I, P, P, P, P, SZ, P, P],
+    "mlvae_log_softmax_fwd": [I, I, P, P, P],
+    "mlvae_log_softmax_bwd": [I, I, P, P, P, P],
     # the feature front end (csrc/fbank.hip)
     "mlvae_fbank_table_size": [I, I, I],
     "mlvae_fbank_workspace_size": [I, I, I, I],
@@ -198,6 +208,8 @@ _RESTYPE = {
     "mlvae_lattice_workspace_size": SZ,
     "mlvae_hmm_viterbi_workspace_size": SZ,
     "mlvae_center_lsm_workspace_size": SZ,
+    "mlvae_edit_align_workspace_size": SZ,
+    "mlvae_ctc_viterbi_workspace_size": SZ,
     "mlvae_fbank_table_size": SZ,
     "mlvae_fbank_workspace_size": SZ,
 }

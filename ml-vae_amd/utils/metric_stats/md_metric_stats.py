@@ -1,5 +1,9 @@
-"""Mispronunciation-detection scores (semantics of ref:src/utils/metric_stats/md_metric_stats.py,
-for the arguments the MD-VAE recipe passes; the PER branch is not part of this build).
+"""Mispronunciation-detection scores (semantics of ref:src/utils/metric_stats/md_metric_stats.py).
+Two ways in: MD label sequences (the MD-VAE recipes), or phoneme sequences aligned to the canonical
+one -- the PER branch the CRDNN_CTC recipes use: the MD labels follow from ``!= canonical`` and
+correct_per / misp_per (per_scoring) join the scores.  The aligned path also comes as device
+tensors (``append_aligned``: ops.ctc_md_counts' integers and the sequences behind them), kept on
+the device and read once per stage.
 
 Labels: 0 = pronounced correctly, 1 = mispronounced; the positive class of PRE / REC / F1 is the
 mispronounced one.  Every ratio carries the reference's eps = 1e-6 and is a percentage; all sums
@@ -8,9 +12,10 @@ import numpy as np
 import torch
 
 from utils.data_utils import boundary_seq_to_seg_seq
-from utils.metric_stats.base_metric_stats import BaseMetricStats, CountsMixin, drop_pad
+from utils.metric_stats.base_metric_stats import PAD_ID, BaseMetricStats, CountsMixin, drop_pad
 
 EPS = 1e-6
+SEQ_KEYS = ("gt_phn_seqs", "gt_cnncl_seqs", "gt_md_lbl_seqs", "pred_phn_seqs", "pred_md_lbl_seqs")
 
 
 class MDMetricStats(CountsMixin, BaseMetricStats):
@@ -37,10 +42,83 @@ class MDMetricStats(CountsMixin, BaseMetricStats):
             for key in self.saved_seqs:
                 self.saved_seqs[key].extend(seqs[key])
 
+    def clear(self):
+        super().clear()
+        self._aligned = []
+
+    def append_aligned(self, ids, counts, ali, phns, cnncls, pred_boundary=None, gt_boundary=None,
+                       batch_index=None):
+        """The PER branch from device tensors, nothing read here: counts [B, 8] int32
+        (ops.ctc_md_counts), ali [B, L] int32 (the prediction aligned to the pronounced sequence,
+        -1 = deleted), phns / cnncls [B, L] ids; the utterance's length is counts[:, 4] +
+        counts[:, 6].  With pred_boundary [B, T] int32 (ops.ctc_viterbi: -1 past T_i) and
+        gt_boundary [B, T] the soft scores of boundary_md_scoring join, as in append."""
+        B = len(ids)
+        if counts.dim() != 2 or tuple(counts.shape) != (B, 8):
+            raise ValueError(f"counts must be [{B}, 8], got {tuple(counts.shape)}")
+        for name, x in (("ali", ali), ("phns", phns), ("cnncls", cnncls)):
+            if x.dim() != 2 or x.shape[0] != B or x.shape[1] != ali.shape[1]:
+                raise ValueError(f"{name} must be [{B}, {ali.shape[1]}], got {tuple(x.shape)}")
+        if (pred_boundary is None) != (gt_boundary is None):
+            raise ValueError("pred_boundary and gt_boundary come together")
+        if pred_boundary is not None and (pred_boundary.dim() != 2 or pred_boundary.shape[0] != B or
+                                          tuple(gt_boundary.shape) != tuple(pred_boundary.shape)):
+            raise ValueError(f"pred_boundary and gt_boundary must both be [{B}, T], got "
+                             f"{tuple(pred_boundary.shape)} and {tuple(gt_boundary.shape)}")
+        self._aligned.append((list(ids), [None if x is None else x.detach() for x in
+                                          (counts, ali, phns, cnncls, pred_boundary, gt_boundary)],
+                              batch_index))
+
+    def _flush_counts(self):
+        super()._flush_counts()
+        pending, self._aligned = self._aligned, []
+        for ids, tensors, batch_index in pending:
+            counts, ali, phns, cnncls, pb, gb = (None if x is None else x.cpu() for x in tensors)
+            keep = [i for i, u in enumerate(ids) if u != PAD_ID]
+            scores = counts_md_scoring(counts[:, :4])
+            seqs = {k: [] for k in SEQ_KEYS}
+            for i in keep:
+                n = int(counts[i, 4] + counts[i, 6])
+                hyp, phn, cn = (x[i, :n].tolist() for x in (ali, phns, cnncls))
+                pred_md, gt_md = [int(h != c) for h, c in zip(hyp, cn)], [int(p != c) for p, c in zip(phn, cn)]
+                if pb is not None:
+                    Tb = int((pb[i] >= 0).sum())
+                    if int((pb[i, :Tb] == 1).sum()) != n or int((gb[i, :Tb] == 1).sum()) != n:
+                        raise ValueError(f"{ids[i]}: {int((pb[i, :Tb] == 1).sum())} predicted and "
+                                         f"{int((gb[i, :Tb] == 1).sum())} true boundaries for {n} phonemes "
+                                         f"in {Tb} frames (an utterance too short for its CTC chain?)")
+                    scores[i].update(boundary_md_scoring(pb[i, :Tb], gb[i, :Tb], pred_md, gt_md))
+                scores[i].update(counts_per_scoring(counts[i, 4:8]))
+                for k, v in zip(SEQ_KEYS, (phn, cn, gt_md, hyp, pred_md)):
+                    seqs[k].append(v)
+            ids = [ids[i] for i in keep]
+            self._extend(ids, [scores[i] for i in keep], batch_index)
+            if ids:
+                seqs["utt_ids"] = ids
+                if not self.saved_seqs:
+                    self.saved_seqs = seqs
+                else:
+                    for key in self.saved_seqs:
+                        self.saved_seqs[key].extend(seqs[key])
+
     def state(self):
         st = super().state()
         st["saved_seqs"] = self.saved_seqs
         return st
+
+    def write_seqs_to_file(self, path):
+        """One block per utterance: its id, then the pronounced, canonical and aligned predicted
+        phoneme ids (-1 = deleted) and the true and predicted MD labels, a row each."""
+        self._flush_counts()
+        s = self.saved_seqs
+        rows = (("phn", "gt_phn_seqs"), ("cnncl", "gt_cnncl_seqs"), ("pred_phn", "pred_phn_seqs"),
+                ("md_lbl", "gt_md_lbl_seqs"), ("pred_md_lbl", "pred_md_lbl_seqs"))
+        with open(path, "w") as f:
+            for i, u in enumerate(s.get("utt_ids", [])):
+                f.write(f"ID: {u}\n")
+                for name, key in rows:
+                    f.write(f"{name}: " + " ".join(str(int(v)) for v in s[key][i]) + "\n")
+                f.write("\n")
 
     def merge(self, states):
         perm = super().merge(states)
@@ -159,10 +237,69 @@ def boundary_md_scoring(pred_boundary_seq, gt_boundary_seq, pred_md_lbl_seq, gt_
     }
 
 
+def _int_1d(x):
+    """list / ndarray / tensor of ids -> 1-D int32 tensor."""
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(x)
+    elif isinstance(x, list):
+        x = torch.Tensor(x)
+    elif not isinstance(x, torch.Tensor):
+        raise TypeError(f"Unsupported input type: {type(x).__name__}")
+    x = x.int().squeeze()
+    if x.ndim > 1:
+        raise ValueError("Only one-dimension input is allowed")
+    return x.reshape(-1)
+
+
+def _per(wrong, n):
+    return wrong / (n + 1e-5) * 100
+
+
+def per_scoring(pred_phn_seq, gt_phn_seq, gt_cnncl_seq):
+    """Error rate of the aligned prediction against the pronounced phonemes, over the positions
+    pronounced canonically (correct_per) and over the mispronounced ones (misp_per); eps = 1e-5."""
+    pred, gt, cn = _int_1d(pred_phn_seq), _int_1d(gt_phn_seq), _int_1d(gt_cnncl_seq)
+    if not len(gt) == len(cn) == len(pred):
+        raise ValueError(f"Inconsistent lengths: {len(gt)}, {len(cn)}, {len(pred)}")
+    ok, bad = torch.where(gt == cn)[0], torch.where(gt != cn)[0]
+    return {"correct_per": _per(torch.sum(pred[ok] != gt[ok]), len(ok)),
+            "misp_per": _per(torch.sum(pred[bad] != gt[bad]), len(bad))}
+
+
+def counts_per_scoring(c):
+    """per_scoring from (canonical positions, of them wrong, mispronounced positions, of them
+    wrong): the same int64 / fp32 arithmetic."""
+    n_ok, w_ok, n_bad, w_bad = (int(v) for v in c)
+    return {"correct_per": _per(torch.tensor(w_ok), n_ok), "misp_per": _per(torch.tensor(w_bad), n_bad)}
+
+
+def _md_labels(phn_seqs, cnncl_seqs):
+    if phn_seqs is None or cnncl_seqs is None:
+        raise ValueError("MD labels need either label sequences or phoneme and canonical sequences")
+    if len(phn_seqs) != len(cnncl_seqs):
+        raise ValueError(f"Inconsistent batch size: {len(phn_seqs)} != {len(cnncl_seqs)}")
+    out = []
+    for p, c in zip(phn_seqs, cnncl_seqs):
+        if len(p) != len(c):
+            raise ValueError(f"Inconsistent sequence lengths: {len(p)} != {len(c)}")
+        out.append([int(a != b) for a, b in zip(p, c)])  # 0 = pronounced correctly, 1 = mispronounced
+    return out
+
+
 def batch_seq_md_scoring(pred_md_lbl_seqs=None, gt_md_lbl_seqs=None, pred_boundary_seqs=None,
-                         gt_boundary_seqs=None, boundary_md_scoring_tol=5):
+                         gt_boundary_seqs=None, boundary_md_scoring_tol=5, pred_phn_seqs=None,
+                         gt_phn_seqs=None, gt_cnncl_seqs=None):
     """Scores of a batch: (one dict per utterance, the sequences kept for the result file).
-    With boundary sequences given, the soft scores join the plain ones."""
+    With boundary sequences given, the soft scores join the plain ones.  MD label sequences that
+    are not given follow from the (aligned) phoneme sequences against the canonical one; with all
+    three phoneme sequences given, correct_per / misp_per join too."""
+    for x in (pred_phn_seqs, gt_phn_seqs, gt_cnncl_seqs):
+        if x is not None and not isinstance(x, list):
+            raise TypeError(f"Input type must be list, not {type(x).__name__}")
+    if pred_md_lbl_seqs is None and pred_phn_seqs is not None:
+        pred_md_lbl_seqs = _md_labels(pred_phn_seqs, gt_cnncl_seqs)
+    if gt_md_lbl_seqs is None and gt_phn_seqs is not None:
+        gt_md_lbl_seqs = _md_labels(gt_phn_seqs, gt_cnncl_seqs)
     for x in (pred_md_lbl_seqs, gt_md_lbl_seqs):
         if not isinstance(x, list):
             raise TypeError(f"Input type must be list, not {type(x).__name__}")
@@ -174,14 +311,20 @@ def batch_seq_md_scoring(pred_md_lbl_seqs=None, gt_md_lbl_seqs=None, pred_bounda
         if pred_boundary_seqs is not None:
             s.update(boundary_md_scoring(pred_boundary_seqs[i], gt_boundary_seqs[i], pred, gt,
                                          boundary_md_scoring_tol))
+        if pred_phn_seqs is not None and gt_phn_seqs is not None and gt_cnncl_seqs is not None:
+            s.update(per_scoring(pred_phn_seqs[i], gt_phn_seqs[i], gt_cnncl_seqs[i]))
         scores.append(s)
-    # no phoneme sequences in this recipe: the reference fills them with its 'sil' id
+    # a phoneme sequence that is not given: the reference fills it with its 'sil' id
     sil = [[7] * len(p) for p in pred_md_lbl_seqs]
+
+    def kept(x):
+        return [list(s) for s in (sil if x is None else x)]
+
     seqs = {
-        "gt_phn_seqs": [list(s) for s in sil],
-        "gt_cnncl_seqs": [list(s) for s in sil],
+        "gt_phn_seqs": kept(gt_phn_seqs),
+        "gt_cnncl_seqs": kept(gt_cnncl_seqs),
         "gt_md_lbl_seqs": list(gt_md_lbl_seqs),
-        "pred_phn_seqs": [list(s) for s in sil],
+        "pred_phn_seqs": kept(pred_phn_seqs),
         "pred_md_lbl_seqs": list(pred_md_lbl_seqs),
     }
     return scores, seqs
