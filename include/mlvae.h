@@ -956,6 +956,54 @@ int mlvae_fbank(int B, int Nmax, const float* wav, int ld, const int* n_samples,
                 int n_fft, int n_mels, const float* table, float* out, int ldo, int* frames, void* ws,
                 size_t ws_bytes, void* stream);
 
+/* The Kaldi-compatible front end (csrc/kaldi_fbank.hip): what the reference's `kaldi_feat` holds
+ * (ref:src/utils/data_io_utils.py:150-206): compute-fbank-feats --window-type=hamming
+ * --htk-compat=true --dither=0.0 --energy-floor=1.0 --snip-edges=false, add-deltas, and per-speaker
+ * compute-cmvn-stats / apply-cmvn --norm-vars=true, restated from Kaldi's documented behaviour
+ * (parity with Kaldi unpinned: no Kaldi binary is among the pinned references; the pin is
+ * tests/kaldi_fbank_ref.py in float64).
+ * wav [B, Nmax] fp32 (row stride ld), n_samples [B] int32 on the device (clamped to [0, Nmax]);
+ * hop and L (the window) in samples, P the power of two at or above L.  Per utterance:
+ * T_b = (N_b + hop/2) / hop frames; frame f covers samples hop f + hop/2 - L/2 + i, i = 0..L-1, an
+ * index outside [0, N_b) mirrored at the ends until it is inside (nothing at or past N_b is read);
+ * per frame the mean is subtracted, then pre-emphasis 0.97 (w[i] -= 0.97 w[i-1], w[0] -= 0.97 w[0]),
+ * the symmetric Hamming window, zero padding to P; |X_k|^2 for k = 0 .. P/2 - 1; n_mels triangular
+ * filters on the 1127 ln(1 + f/700) mel scale from 20 Hz to sample_rate/2; ln(max(e, FLT_EPSILON));
+ * delta_t = sum_{j=-2..2} j x_{clamp(t+j, 0, T_b-1)} / 10; delta-delta = the 9 taps
+ * [4 4 1 -4 -10 -4 1 4 4] / 100 on the statics at clamped indices.
+ * out [B, Tmax, 3 n_mels] (row stride ldo, Tmax = (Nmax + hop/2) / hop) = (static | delta |
+ * delta-delta), or [B, Tmax, n_mels] with deltas = 0; rows t >= T_b exact zeros; frames [B] = T_b.
+ * N_b < hop/2 gives no frame.  fp32 operands and accumulation (exact-f32 MFMA); no floating-point
+ * atomics and tiles are per utterance: a rerun is bit-identical and an utterance's rows do not
+ * depend on the rest of the batch.
+ * Limits (status 1): 2 <= L <= P <= 512 with P a power of two, 1 <= n_mels <= 64, hop >= 1,
+ * B <= 65535.  B == 0 is a no-op.
+ * mlvae_kaldi_fbank_table fills a HOST buffer of mlvae_kaldi_fbank_table_size(L, P, n_mels) bytes
+ * (float64 arithmetic, rounded to fp32); the caller uploads it once per geometry.  ws:
+ * mlvae_kaldi_fbank_workspace_size(B, Nmax, hop, n_mels) bytes (the log-mel frames).  The size
+ * functions return 0 for a geometry outside the limits (mlvae_last_error says why).
+ *
+ * Per-speaker CMVN over feats [B, T, D] fp32 (row stride ld), frames [B] and spk [B] int32 on the
+ * device, stats [S, 2 D + 1] float64 on the device, owned by the caller = (sum x | sum x^2 | n).
+ * mlvae_cmvn_accumulate adds the batch's valid rows into stats: one workgroup per speaker walks the
+ * utterances in row order and their frames in time order (a fixed order, no floating-point
+ * atomics: a rerun is bit-identical).  mlvae_cmvn_apply, in place on rows t < frames[b]:
+ * mean = sum x / n, var = max(sum x^2 / n - mean^2, 1e-20), y = (x - mean) / sqrt(var); rows past
+ * frames[b] are not touched.  err: a device int32 word the kernels OR into: bit 0 a speaker id
+ * outside [0, S) (that utterance is skipped), bit 1 (apply) a speaker with n = 0 (left as it is).
+ * Limits (status 1): D <= 1024, S >= 1, B <= 65535. */
+size_t mlvae_kaldi_fbank_table_size(int L, int P, int n_mels);
+size_t mlvae_kaldi_fbank_workspace_size(int B, int Nmax, int hop, int n_mels);
+int mlvae_kaldi_fbank_table(int sample_rate, int L, int P, int n_mels, float* host_table,
+                            size_t table_bytes);
+int mlvae_kaldi_fbank(int B, int Nmax, const float* wav, int ld, const int* n_samples, int hop, int L,
+                      int P, int n_mels, int deltas, const float* table, float* out, int ldo,
+                      int* frames, void* ws, size_t ws_bytes, void* stream);
+int mlvae_cmvn_accumulate(int B, int T, int D, int S, const float* feats, int ld, const int* frames,
+                          const int* spk, double* stats, int* err, void* stream);
+int mlvae_cmvn_apply(int B, int T, int D, int S, float* feats, int ld, const int* frames,
+                     const int* spk, const double* stats, int* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

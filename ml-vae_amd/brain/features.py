@@ -8,7 +8,10 @@ epoch < update_until_epoch; x <- (x - mean) / std.  Device-side torch ops with n
 synchronisation (outside the fused train step, which takes already normalised features).
 
 Fbank: the reference's compute_features (ref:src/config/run.yaml:39-44), waveform -> log-mel
-filterbank + deltas + delta-deltas on the HIP kernels of csrc/fbank.hip."""
+filterbank + deltas + delta-deltas on the HIP kernels of csrc/fbank.hip.
+
+KaldiFbank and SpeakerCMVN: the reference's `kaldi_feat` (ref:src/utils/data_io_utils.py:150-206),
+Kaldi's filterbank + add-deltas and the per-speaker CMVN on the kernels of csrc/kaldi_fbank.hip."""
 import torch
 
 
@@ -128,3 +131,73 @@ class Fbank(torch.nn.Module):
                              win_length=self.win_length, n_fft=self.n_fft, n_mels=self.n_mels,
                              f_min=self.f_min, f_max=self.f_max)
         return feats if self.deltas else feats[..., :self.n_mels]
+
+
+class KaldiFbank(torch.nn.Module):
+    """What the reference's Kaldi binaries compute before CMVN (kaldi_feature_params of
+    ref:src/config/run.yaml, run by ref:src/utils/data_io_utils.py:150-206): compute-fbank-feats
+    --window-type=hamming --htk-compat=true --dither=0.0 --energy-floor=1.0 --snip-edges=false and
+    add-deltas, waveform [B, N] -> [B, T, 3 n_mels] (static | delta | delta-delta; [B, T, n_mels]
+    with deltas=False), T = (N + hop/2) // hop.  The constructor keys are the reference's:
+    hop_length in milliseconds, n_fft the frame length in samples (the frame length is
+    n_fft / sample_rate, ref:src/utils/data_io_utils.py:161).  Kaldi's documented behaviour restated
+    (parity with Kaldi unpinned, include/mlvae.h mlvae_kaldi_fbank); the work is two HIP kernels
+    (mlvae_hip.ops.kaldi_fbank), per utterance as in Fbank: with wav_lens (relative,
+    N_b = round(N len_b)) the mirrored edges and the delta edges are those of the unpadded waveform
+    and the rows past (N_b + hop/2) // hop are zeros.  The per-speaker normalisation is SpeakerCMVN.
+    Constructing it touches neither the device nor a random generator."""
+
+    def __init__(self, sample_rate=16000, hop_length=20, n_fft=400, n_mels=40, deltas=True):
+        super().__init__()
+        self.sample_rate, self.n_fft, self.n_mels = int(sample_rate), int(n_fft), int(n_mels)
+        self.hop_length = hop_length
+        self.win_length = 1000.0 * self.n_fft / self.sample_rate  # milliseconds
+        self.deltas = bool(deltas)
+
+    def frames(self, n_samples):
+        """Frames of an utterance of n_samples samples."""
+        hop = int(round(self.sample_rate / 1000.0 * self.hop_length))
+        return (int(n_samples) + hop // 2) // hop
+
+    @torch.no_grad()
+    def forward(self, wav, wav_lens=None):
+        from mlvae_hip import ops
+        if wav_lens is not None:
+            wav_lens = torch.as_tensor(wav_lens, dtype=torch.float32)
+        feats, _ = ops.kaldi_fbank(wav, wav_lens, sample_rate=self.sample_rate, hop_length=self.hop_length,
+                                   win_length=self.win_length, n_mels=self.n_mels, deltas=self.deltas)
+        return feats
+
+
+class SpeakerCMVN:
+    """Kaldi's per-speaker compute-cmvn-stats + apply-cmvn --norm-vars=true over one split: holds
+    the float64 statistics [n_speakers, 2 dim + 1] = (sum x | sum x^2 | n) on the device.
+    accumulate(feats [B, T, dim], frames [B], spk [B]) adds a batch's valid rows (fixed order: a
+    rerun is bit-identical); apply(...) normalises the valid rows in place with each utterance's
+    speaker's mean and variance (floored at 1e-20) and returns feats; reset() zeroes the
+    statistics.  The buffer is created on the first batch's device."""
+
+    def __init__(self, n_speakers, dim):
+        self.n_speakers, self.dim = int(n_speakers), int(dim)
+        if self.n_speakers < 1 or self.dim < 1:
+            raise ValueError("SpeakerCMVN: n_speakers and dim must be >= 1")
+        self.stats = None
+
+    def _buffer(self, dev):
+        if self.stats is None or self.stats.device != dev:
+            self.stats = torch.zeros(self.n_speakers, 2 * self.dim + 1, device=dev, dtype=torch.float64)
+        return self.stats
+
+    def reset(self):
+        if self.stats is not None:
+            self.stats.zero_()
+
+    @torch.no_grad()
+    def accumulate(self, feats, frames, spk):
+        from mlvae_hip import ops
+        ops.cmvn_accumulate(self._buffer(feats.device), feats, frames, spk)
+
+    @torch.no_grad()
+    def apply(self, feats, frames, spk):
+        from mlvae_hip import ops
+        return ops.cmvn_apply(feats, frames, spk, self._buffer(feats.device))

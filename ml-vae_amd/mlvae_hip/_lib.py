@@ -187,6 +187,13 @@ _SIGS = {
     "mlvae_fbank_workspace_size": [I, I, I, I],
     "mlvae_fbank_table": [I, I, I, I, F, F, P, SZ],
     "mlvae_fbank": [I, I, P, I, P, I, I, I, I, P, P, I, P, P, SZ, P],
+    # the Kaldi-compatible front end and per-speaker CMVN (csrc/kaldi_fbank.hip)
+    "mlvae_kaldi_fbank_table_size": [I, I, I],
+    "mlvae_kaldi_fbank_workspace_size": [I, I, I, I],
+    "mlvae_kaldi_fbank_table": [I, I, I, I, P, SZ],
+    "mlvae_kaldi_fbank": [I, I, P, I, P, I, I, I, I, I, P, P, I, P, P, SZ, P],
+    "mlvae_cmvn_accumulate": [I, I, I, I, P, I, P, P, P, P, P],
+    "mlvae_cmvn_apply": [I, I, I, I, P, I, P, P, P, P, P],
 }
 _RESTYPE = {
     "mlvae_last_error": C.c_char_p,
@@ -212,6 +219,8 @@ _RESTYPE = {
     "mlvae_ctc_viterbi_workspace_size": SZ,
     "mlvae_fbank_table_size": SZ,
     "mlvae_fbank_workspace_size": SZ,
+    "mlvae_kaldi_fbank_table_size": SZ,
+    "mlvae_kaldi_fbank_workspace_size": SZ,
 }
 
 _lib = None

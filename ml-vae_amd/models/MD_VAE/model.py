@@ -129,9 +129,8 @@ class SBModel(MDModel):
         target = self.target
         noise = self.noise or {}
         batch = batch.to(self.device)
-        feats, feat_lens = batch["feat"]
+        feats, feat_lens = self._input_feats(batch)
         predictions = {"losses": {}}
-        feats = self.hparams.normalizer(feats, feat_lens, epoch=self.hparams.epoch_counter.current)
         feats = feats.contiguous()
 
         def run(trained, fn):
@@ -156,6 +155,18 @@ class SBModel(MDModel):
             predictions["boundary_v"] = bnd["boundary_v"]
             predictions["losses"].update(bnd["losses"])
         return predictions, batch, feats, feat_lens, noise
+
+    def _feat_field(self):
+        """The batch field the recipe reads its input frames and their lengths from."""
+        return "feat"
+
+    def _input_feats(self, batch):
+        """(input frames, relative lengths): batch['feat'] through the normaliser."""
+        feats, feat_lens = batch["feat"]
+        return self.hparams.normalizer(feats, feat_lens, epoch=self.hparams.epoch_counter.current), feat_lens
+
+    def _dp_lens_field(self, batch, stage):
+        return self._feat_field()
 
     def _pi_logits(self, predictions, feats, phn_fc):
         """feat_fc + the recogniser output's FC (module name phn_fc) -> concat_fc -> rnn -> pi_fc:
@@ -195,7 +206,7 @@ class SBModel(MDModel):
 
     # ------------------------------------------------------------------ objectives
     def compute_objectives(self, predictions, batch, stage):
-        feats, feat_lens = batch["feat"]
+        feats, feat_lens = batch[self._feat_field()]
         losses = {key: apply_lens_to_loss(value, feat_lens)
                   for key, value in predictions["losses"].items()}
         loss = self.compute_and_save_losses(losses)

@@ -20,6 +20,9 @@ has its own noise, as K independent passes have in distribution.  The score-func
 one fused kernel each way (ops.sfl_losses).
 
 ``self.noise`` (tests): as MD_VAE's, with pi_u [K,B,T] and eps_v, eps_g, expo with a leading K.
+``use_kaldi_feat: true`` (the reference's MD_VAE_sfl default; here an override, as the yaml's key
+set is the recipe's without it): the input is batch['kaldi_feat'] and the normaliser is not run.
+
 Data parallel (models/md_model.py's shard-exact step): the K B fold runs under the shard context's
 folded(K) variant, so row k B_l + b draws what the single process draws at row k B_g + b_g.
 """
@@ -31,6 +34,23 @@ from models.MD_VAE.model import Target
 
 
 class SBModel(MD_VAE):
+    def _use_kaldi_feat(self):
+        return getattr(self.hparams, "use_kaldi_feat", False) is True
+
+    def _feat_field(self):
+        return "kaldi_feat" if self._use_kaldi_feat() else "feat"
+
+    def _input_feats(self, batch):
+        """use_kaldi_feat (ref:src/models/MD_VAE_sfl/model.py:59-63): the corpus's already
+        normalised `kaldi_feat`, the normaliser not called; else `feat` through the normaliser."""
+        if not self._use_kaldi_feat():
+            return super()._input_feats(batch)
+        if "kaldi_feat" not in batch:
+            raise ValueError("use_kaldi_feat: the batch has no kaldi_feat field; build the corpus with "
+                             "synthetic: {kaldi_feats: true} (with waveforms: true), or point "
+                             "prepare.dataset_dir at a computed dataset that holds it")
+        return batch["kaldi_feat"]
+
     def compute_forward(self, batch, stage):
         predictions, batch, feats, feat_lens, noise = self._upstream(batch)
         if self.target in (Target.VAE, Target.TEST):

@@ -17,7 +17,9 @@
   gt_boundary_seq segment in samples (the HMM_DNN_ALI aligner's ground truth), derived too.
   ``waveforms=True`` (``synthetic.waveforms``) with md_labels makes the corpus spoken: wav and
   gt_phn_seq from a third generator per utterance, feat = compute_features(wav) (the Fbank front
-  end, brain.features.Fbank) -- see SyntheticSet.
+  end, brain.features.Fbank) -- see SyntheticSet.  ``kaldi_feats=True``
+  (``synthetic.kaldi_feats``) with waveforms adds spk and kaldi_feat, the Kaldi-compatible front
+  end with per-speaker CMVN (brain.features.KaldiFbank, SpeakerCMVN).
 
 Batches follow SpeechBrain's PaddedBatch: batch['feat'] = (padded [B, Tmax, F], relative lengths
 [B]).  Under data parallelism rank r of W reads utterances [r*bs, (r+1)*bs) of every global batch
@@ -294,10 +296,9 @@ def _spoken_utterance(e, n_phonemes, samples_per_frame, sample_rate, g):
     return phn, torch.from_numpy((wav + WAV_NOISE * noise).astype(np.float32))
 
 
-def _spoken_features(items, compute_features, feat_dim):
-    """feat = compute_features(wav) of every utterance, in padded batches of WAV_BATCH, trimmed to
-    the labels' T frames (the front end yields T + 1; ref:src/utils/data_io.py:199-201 trims the
-    same way), kept on the host as the random features are."""
+def _wav_batches(items):
+    """(utterances, padded wav [B, N], relative lengths [B]) in batches of WAV_BATCH, on the device
+    when there is one."""
     dev = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
     for i in range(0, len(items), WAV_BATCH):
         part = items[i:i + WAV_BATCH]
@@ -306,7 +307,15 @@ def _spoken_features(items, compute_features, feat_dim):
         for j, e in enumerate(part):
             wav[j, :e["wav"].shape[0]] = e["wav"]
         lens = torch.tensor([e["wav"].shape[0] / N for e in part], dtype=torch.float32)
-        feats = torch.as_tensor(compute_features(wav.to(dev), lens.to(dev))).detach().cpu().float()
+        yield part, wav.to(dev), lens.to(dev)
+
+
+def _spoken_features(items, compute_features, feat_dim):
+    """feat = compute_features(wav) of every utterance, in padded batches of WAV_BATCH, trimmed to
+    the labels' T frames (the front end yields T + 1; ref:src/utils/data_io.py:199-201 trims the
+    same way), kept on the host as the random features are."""
+    for part, wav, lens in _wav_batches(items):
+        feats = torch.as_tensor(compute_features(wav, lens)).detach().cpu().float()
         for j, e in enumerate(part):
             T = e["feat"].shape[0]
             if feats.dim() != 3 or feats.shape[1] < T:
@@ -318,6 +327,34 @@ def _spoken_features(items, compute_features, feat_dim):
             e["feat"] = feats[j, :T].clone()
 
 
+def _kaldi_features(items, compute_kaldi_features, cmvn, n_speakers):
+    """spk = utterance index % n_speakers and kaldi_feat = the Kaldi-compatible front end with
+    per-speaker CMVN over the split (ref:src/utils/data_io_utils.py:150-206), in two passes of
+    WAV_BATCH-sized batches: the raw features and the speakers' statistics, then the normalisation.
+    `items` is in utterance order.  T samples_per_frame samples give exactly T frames."""
+    for i, e in enumerate(items):
+        e["spk"] = i % n_speakers
+    cmvn.reset()
+    raw = []
+    for part, wav, lens in _wav_batches(items):
+        feats = torch.as_tensor(compute_kaldi_features(wav, lens)).detach().float()
+        frames = [e["feat"].shape[0] for e in part]
+        if feats.dim() != 3 or feats.shape[1] != max(frames):
+            raise ValueError(f"synthetic corpus: compute_kaldi_features gave {tuple(feats.shape)} for "
+                             f"utterances of up to {max(frames)} frames (hop_length must be "
+                             "samples_per_frame samples)")
+        if feats.shape[2] != cmvn.dim:
+            raise ValueError(f"synthetic corpus: compute_kaldi_features gives {feats.shape[2]}-d frames, "
+                             f"the model's input_size is {cmvn.dim}")
+        spk = [e["spk"] for e in part]
+        cmvn.accumulate(feats, frames, spk)
+        raw.append((part, feats.cpu(), frames, spk, feats.device))
+    for part, feats, frames, spk, dev in raw:
+        feats = torch.as_tensor(cmvn.apply(feats.to(dev), frames, spk)).detach().cpu().float()
+        for j, e in enumerate(part):
+            e["kaldi_feat"] = feats[j, :frames[j]].clone()
+
+
 class SyntheticSet:
     """waveforms=True (``synthetic.waveforms``, with md_labels) makes the corpus *spoken*: every
     utterance gets gt_phn_seq (the pronounced ids: canonical where plvl_gt_md_lbl_seq is 0,
@@ -326,13 +363,29 @@ class SyntheticSet:
     compute_features(wav) -- so the features carry the labels.  Every other field keeps the value
     it has without waveforms: the feature generator still takes its draws and the new fields come
     from a generator of their own per utterance.  Under data parallelism every rank builds the
-    same corpus (nothing here depends on the rank) and reads its slice of each batch."""
+    same corpus (nothing here depends on the rank) and reads its slice of each batch.
+
+    kaldi_feats=True (``synthetic.kaldi_feats``, with waveforms) adds two fields and changes no
+    other: spk = utterance index % n_speakers, and kaldi_feat [T, feat_dim] float32 =
+    compute_kaldi_features(wav) (brain.features.KaldiFbank) normalised per speaker over the split
+    (`speaker_cmvn`: an object with reset / accumulate / apply, brain.features.SpeakerCMVN when
+    None) -- the reference's `kaldi_feat`, which MD_VAE_sfl reads under use_kaldi_feat."""
 
     def __init__(self, n_utts, feat_dim, min_frames, max_frames, seed, sorting="descending",
                  md_labels=False, n_phonemes=39, phn_labels=False, ali_labels=False,
-                 samples_per_frame=320, waveforms=False, compute_features=None, sample_rate=16000):
+                 samples_per_frame=320, waveforms=False, compute_features=None, sample_rate=16000,
+                 kaldi_feats=False, n_speakers=4, compute_kaldi_features=None, speaker_cmvn=None):
         if ali_labels and not md_labels:
             raise ValueError("synthetic corpus: ali_labels needs md_labels")
+        if kaldi_feats:
+            if not waveforms:
+                raise ValueError("synthetic corpus: kaldi_feats needs waveforms (kaldi_feat is computed "
+                                 "from the synthesised waveform)")
+            if compute_kaldi_features is None:
+                raise ValueError("synthetic corpus: kaldi_feats needs compute_kaldi_features "
+                                 "(config/run.yaml's compute_kaldi_features: the KaldiFbank front end)")
+            if int(n_speakers) < 1:
+                raise ValueError(f"synthetic corpus: n_speakers = {n_speakers} must be >= 1")
         if waveforms:
             if not md_labels:
                 raise ValueError("synthetic corpus: waveforms needs md_labels (the waveform is "
@@ -364,6 +417,11 @@ class SyntheticSet:
                 e["gt_phn_seq"], e["wav"] = _spoken_utterance(e, n_phonemes, int(samples_per_frame),
                                                               int(sample_rate), _wave_generator(seed, i))
             _spoken_features(self.items, compute_features, feat_dim)
+        if kaldi_feats:
+            if speaker_cmvn is None:
+                from brain.features import SpeakerCMVN
+                speaker_cmvn = SpeakerCMVN(int(n_speakers), feat_dim)
+            _kaldi_features(self.items, compute_kaldi_features, speaker_cmvn, int(n_speakers))
         _sort(self.items, sorting)
         self.sorting = sorting
 
@@ -404,5 +462,8 @@ def prepare_datasets(hparams):
                                  int(hparams.get("hop_length", 20)) // 1000,
                                  waveforms=bool(d.get("waveforms", False)),
                                  compute_features=hparams.get("compute_features"),
-                                 sample_rate=int(hparams.get("sample_rate", 16000))))
+                                 sample_rate=int(hparams.get("sample_rate", 16000)),
+                                 kaldi_feats=bool(d.get("kaldi_feats", False)),
+                                 n_speakers=int(d.get("n_speakers", 4)),
+                                 compute_kaldi_features=hparams.get("compute_kaldi_features")))
     return sets, None
