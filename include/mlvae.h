@@ -1004,6 +1004,52 @@ int mlvae_cmvn_accumulate(int B, int T, int D, int S, const float* feats, int ld
 int mlvae_cmvn_apply(int B, int T, int D, int S, float* feats, int ld, const int* frames,
                      const int* spk, const double* stats, int* err, void* stream);
 
+/* ---- The frozen wav2vec2 encoder, forward only (csrc/w2v.hip; DESIGN.md section 4, "The wav2vec2
+ * encoder").  Replaces SpeechBrain's HuggingFaceWav2Vec2(freeze=True) as the reference builds it
+ * (ref:src/models/w2v_MD_VAE/model.yaml:11-16) and calls it (ref:src/models/w2v_MD_VAE/model.py:24).
+ * The matrix products are mlvae_gemm_bf16 / mlvae_gemm (conv layers 1-6 and the positional conv as
+ * GEMMs over overlapping rows: lda < K); these are the kernels between them.  No atomics, fixed
+ * reduction orders: a rerun is bit-identical.
+ *
+ * tensor_stats: stats[0] = mean, stats[1] = 1 / sqrt(biased var + eps) over all n elements of x
+ *   (F.layer_norm(x, x.shape) of normalize_wav / output_norm): fp64 partial sums per workgroup in ws
+ *   (stats_workspace_size bytes, 8-byte aligned), folded in a fixed order.
+ * scale_shift: out = (x - stats[0]) stats[1], n elements (the output norm's apply pass).
+ * conv0: wav [B, N] -> out [B, T0, C] channels-last (fp32, or bf16 with out_bf16):
+ *   GELU(LN_C(conv(K, stride, Cin = 1)((wav - stats[0]) stats[1]) + bias)); stats NULL = the
+ *   waveform as it is; w [C][K].  Limits (conv0_supported): C <= 512, K <= 10; (T0-1) stride + K <= N.
+ * rows: per row of x [N, C] (fp32, leading dimension ldx)
+ *     y = x + bias (bias NULL: none);  gamma != NULL: y = LN_C(y) gamma + beta (C <= 2048);
+ *     (C and the leading dimensions multiples of 4, 16-byte aligned buffers)
+ *     gelu: y = GELU(y) (exact erf);  res != NULL: y += res[row] (res may be out_f32: in place)
+ *   written to out_f32 and / or out_bf16 (leading dimension ldo).  One kernel: the conv stack's
+ *   LN + GELU, the projection's LN, both LNs of a layer, the FFN's GELU, the final LN and the
+ *   positional conv's h += GELU(x + bias).
+ * regroup: h [B, T, C] fp32 -> out [B, G, T + K, C / G] (fp32 or bf16), rows K/2 .. K/2 + T - 1 of
+ *   each group the frames, zeros around them: a positional-conv window is then K C/G contiguous
+ *   elements at frame offset t C/G.
+ * attention: out [B T, H d] = softmax(scale Q K^T) V per (utterance, head), Q / K / V read in place
+ *   from qkv [B T, 3 H d] (fp32, or bf16 with qkv_bf16); no mask; online softmax over streamed
+ *   32-key tiles in fp32 (T is not bounded).  f32_math = 0: bf16 MFMA operands, fp32 accumulate;
+ *   1: the fp32 MFMA (the parity mode).  Limits (attention_supported): d in {32, 64}, H <= 65535
+ *   (and B <= 65535). */
+size_t mlvae_w2v_stats_workspace_size(size_t n);
+int mlvae_w2v_tensor_stats(size_t n, const float* x, float eps, float* stats, void* ws, size_t ws_bytes,
+                           void* stream);
+int mlvae_w2v_scale_shift(size_t n, const float* x, const float* stats, float* out, void* stream);
+int mlvae_w2v_conv0_supported(int C, int K);
+int mlvae_w2v_conv0(int B, int N, int T0, int C, int K, int stride, const float* wav, const float* stats,
+                    const float* w, const float* bias, const float* gamma, const float* beta, float eps,
+                    void* out, int out_bf16, void* stream);
+int mlvae_w2v_rows(int N, int C, const float* x, int ldx, const float* bias, const float* gamma,
+                   const float* beta, float eps, int gelu, const float* res, int ldres, float* out_f32,
+                   void* out_bf16, int ldo, void* stream);
+int mlvae_w2v_regroup(int B, int T, int C, int G, int K, const float* h, void* out, int out_bf16,
+                      void* stream);
+int mlvae_w2v_attention_supported(int T, int H, int d);
+int mlvae_w2v_attention(int B, int T, int H, int d, const void* qkv, int qkv_bf16, int f32_math,
+                        float scale, void* out, int out_bf16, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

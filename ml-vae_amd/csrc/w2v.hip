@@ -1,0 +1,538 @@
+// The frozen wav2vec2 encoder's own kernels (forward only; DESIGN.md section 4, "The wav2vec2
+// encoder").  The matrix products -- conv layers 1-6 and the positional conv as GEMMs over
+// overlapping rows, QKV / out-proj / FFN -- are mlvae_gemm_bf16 / mlvae_gemm; this file holds what
+// sits between them.
+//
+// Reference: the HuggingFace wav2vec2 architecture (stable-layer-norm family) as SpeechBrain's
+// HuggingFaceWav2Vec2 wraps it, built at ref:src/models/w2v_MD_VAE/model.yaml:11-16 and called at
+// ref:src/models/w2v_MD_VAE/model.py:24.  tests/w2v_ref.py restates the forward in plain torch
+// and is the checker of these kernels.
+//
+//   stats_partial / stats_final   mean and rstd of a whole tensor (normalize_wav, output_norm):
+//                                 fp64 partial sums per workgroup, folded in a fixed order
+//   scale_shift_kernel            out = (x - mean) rstd (the output norm's apply pass)
+//   conv0_kernel                  waveform -> [B, T0, C] channels-last: conv(Cin = 1) + bias +
+//                                 LN over C + GELU, one wave per frame, weights in registers
+//   rows_kernel                   y = [res +] [GELU] [LN] (x [+ bias]) per row, fp32 and/or bf16 out,
+//                                 one wave per row, 16-byte accesses
+//   regroup_kernel                h [B, T, C] -> zero-padded group-major [B, G, T + K, C / G]
+//   attention_kernel              softmax(Q K^T) V per (utterance, head), online softmax over
+//                                 streamed 32-key tiles, MFMA both products
+// No atomics; every reduction runs in a fixed order, so the outputs are bit-reproducible.
+#include "common.h"
+
+namespace {
+
+constexpr int NT = 256;
+
+__device__ __forceinline__ float gelu_erf(float x) {
+  return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f));
+}
+
+// ------------------------------------------------------------------ whole-tensor statistics
+constexpr int STATS_MAX_BLOCKS = 1024;
+constexpr int STATS_PER_BLOCK = NT * 16;
+
+int stats_blocks(size_t n) {
+  size_t b = (n + STATS_PER_BLOCK - 1) / STATS_PER_BLOCK;
+  if (b < 1) b = 1;
+  if (b > STATS_MAX_BLOCKS) b = STATS_MAX_BLOCKS;
+  return (int)b;
+}
+
+// workgroup sum of (s, q) in a fixed order; the result is valid on thread 0
+__device__ __forceinline__ void block_sum2(double& s, double& q, double* sh) {
+  s = wave_sum_d(s);
+  q = wave_sum_d(q);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { sh[2 * wave] = s; sh[2 * wave + 1] = q; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    s = ((sh[0] + sh[2]) + sh[4]) + sh[6];
+    q = ((sh[1] + sh[3]) + sh[5]) + sh[7];
+  }
+}
+
+__global__ __launch_bounds__(NT) void stats_partial(size_t n, const float* __restrict__ x,
+                                                    double* __restrict__ part) {
+  __shared__ double sh[8];
+  double s = 0.0, q = 0.0;
+  for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)gridDim.x * NT) {
+    const double v = (double)x[i];
+    s += v;
+    q += v * v;
+  }
+  block_sum2(s, q, sh);
+  if (threadIdx.x == 0) { part[2 * blockIdx.x] = s; part[2 * blockIdx.x + 1] = q; }
+}
+
+__global__ __launch_bounds__(NT) void stats_final(size_t n, int nb, const double* __restrict__ part,
+                                                  float eps, float* __restrict__ stats) {
+  __shared__ double sh[8];
+  double s = 0.0, q = 0.0;
+  for (int i = threadIdx.x; i < nb; i += NT) { s += part[2 * i]; q += part[2 * i + 1]; }
+  block_sum2(s, q, sh);
+  if (threadIdx.x == 0) {
+    const double mean = s / (double)n;
+    double var = q / (double)n - mean * mean;  // biased, as F.layer_norm
+    if (var < 0.0) var = 0.0;
+    stats[0] = (float)mean;
+    stats[1] = (float)(1.0 / sqrt(var + (double)eps));
+  }
+}
+
+__global__ __launch_bounds__(NT) void scale_shift_kernel(size_t n, const float* __restrict__ x,
+                                                         const float* __restrict__ stats,
+                                                         float* __restrict__ out) {
+  const float mean = stats[0], rstd = stats[1];
+  for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)gridDim.x * NT)
+    out[i] = (x[i] - mean) * rstd;
+}
+
+// ------------------------------------------------------------------ conv layer 0
+constexpr int CONV0_KMAX = 10;
+constexpr int CONV0_FRAMES = 16;  // frames per wave
+
+// lane l owns channels l CPL .. l CPL + CPL - 1 (consecutive: a lane's stores of a frame are adjacent)
+template <int CPL, bool OUT_BF16>
+__global__ __launch_bounds__(NT) void conv0_kernel(int B, int N, int T0, int C, int K, int stride,
+                                                   const float* __restrict__ wav,
+                                                   const float* __restrict__ stats,
+                                                   const float* __restrict__ w,
+                                                   const float* __restrict__ bias,
+                                                   const float* __restrict__ gamma,
+                                                   const float* __restrict__ beta, float eps,
+                                                   void* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const long long wave = (long long)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+  const long long frames = (long long)B * T0;
+  const long long f0 = wave * CONV0_FRAMES;
+  if (f0 >= frames) return;
+  float wr[CPL][CONV0_KMAX], br[CPL], gr[CPL], be[CPL];
+#pragma unroll
+  for (int i = 0; i < CPL; ++i) {
+    const int c = lane * CPL + i;
+    const bool ok = c < C;
+#pragma unroll
+    for (int k = 0; k < CONV0_KMAX; ++k) wr[i][k] = (ok && k < K) ? w[(size_t)c * K + k] : 0.f;
+    br[i] = ok ? bias[c] : 0.f;
+    gr[i] = ok ? gamma[c] : 0.f;
+    be[i] = ok ? beta[c] : 0.f;
+  }
+  const float mean = stats ? stats[0] : 0.f, rstd = stats ? stats[1] : 1.f;
+  const float invC = 1.f / (float)C;
+  const long long f1 = f0 + CONV0_FRAMES < frames ? f0 + CONV0_FRAMES : frames;
+  for (long long f = f0; f < f1; ++f) {
+    const int b = (int)(f / T0), t = (int)(f - (long long)b * T0);
+    const float* xw = wav + (size_t)b * N + (size_t)t * stride;  // t stride + K <= N by T0's definition
+    float xv[CONV0_KMAX];
+#pragma unroll
+    for (int k = 0; k < CONV0_KMAX; ++k) xv[k] = k < K ? (xw[k] - mean) * rstd : 0.f;
+    float y[CPL];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+      float a = 0.f;
+#pragma unroll
+      for (int k = 0; k < CONV0_KMAX; ++k) a = fmaf(wr[i][k], xv[k], a);
+      y[i] = a + br[i];
+      if (lane * CPL + i < C) s += y[i];
+    }
+    const float mu = wave_sum(s) * invC;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+      const float d = y[i] - mu;
+      if (lane * CPL + i < C) q += d * d;
+    }
+    const float rs = 1.f / sqrtf(wave_sum(q) * invC + eps);
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) y[i] = gelu_erf((y[i] - mu) * rs * gr[i] + be[i]);
+    const size_t o = (size_t)f * C + (size_t)lane * CPL;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+      if (lane * CPL + i < C) {
+        if constexpr (OUT_BF16) static_cast<short*>(out)[o + i] = f2bf(y[i]);
+        else static_cast<float*>(out)[o + i] = y[i];
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------ the row kernel
+constexpr int ROWS_MAX_LN = 8;  // LN keeps a row in registers: C <= 64 lanes x 4 columns x 8
+
+// one wave per row, lane l at the column quads l, l + 64, ...: 16-byte accesses throughout
+template <bool LN>
+__global__ __launch_bounds__(NT) void rows_kernel(int N, int C, const float* __restrict__ x, int ldx,
+                                                  const float* __restrict__ bias,
+                                                  const float* __restrict__ gamma,
+                                                  const float* __restrict__ beta, float eps, int gelu,
+                                                  const float* res, int ldres, float* out_f32,
+                                                  short* out_bf16, int ldo) {
+  const int lane = threadIdx.x & 63, C4 = C / 4;
+  const long long row = (long long)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+  if (row >= N) return;
+  const f32x4* xr = reinterpret_cast<const f32x4*>(x + (size_t)row * ldx);
+  const f32x4* rr = res ? reinterpret_cast<const f32x4*>(res + (size_t)row * ldres) : nullptr;
+  const f32x4* b4 = reinterpret_cast<const f32x4*>(bias);
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  auto finish = [&](int q, f32x4 y) {
+    if (gelu) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) y[e] = gelu_erf(y[e]);
+    }
+    if (rr) y += rr[q];  // res may be out_f32: this thread's own quad, read before it is written
+    if (out_f32) *reinterpret_cast<f32x4*>(out_f32 + (size_t)row * ldo + 4 * q) = y;
+    if (out_bf16)
+      *reinterpret_cast<bf16x4*>(out_bf16 + (size_t)row * ldo + 4 * q) =
+          bf16x4{f2bf(y[0]), f2bf(y[1]), f2bf(y[2]), f2bf(y[3])};
+  };
+  if constexpr (LN) {
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(gamma);
+    const f32x4* be4 = reinterpret_cast<const f32x4*>(beta);
+    f32x4 v[ROWS_MAX_LN];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < ROWS_MAX_LN; ++i) {
+      const int q = lane + 64 * i;
+      v[i] = q < C4 ? xr[q] + (bias ? b4[q] : zero) : zero;
+      s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+    }
+    const float invC = 1.f / (float)C;
+    const float mu = wave_sum(s) * invC;
+    float sq = 0.f;
+#pragma unroll
+    for (int i = 0; i < ROWS_MAX_LN; ++i) {
+      if (lane + 64 * i < C4) {
+        const f32x4 d = v[i] - mu;
+        sq += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+      }
+    }
+    const float rs = 1.f / sqrtf(wave_sum(sq) * invC + eps);
+#pragma unroll
+    for (int i = 0; i < ROWS_MAX_LN; ++i) {
+      const int q = lane + 64 * i;
+      if (q < C4) finish(q, (v[i] - mu) * rs * g4[q] + be4[q]);
+    }
+  } else {
+    for (int q = lane; q < C4; q += 64) finish(q, xr[q] + (bias ? b4[q] : zero));
+  }
+}
+
+// ------------------------------------------------------------------ positional-conv regroup
+template <bool OUT_BF16>
+__global__ __launch_bounds__(NT) void regroup_kernel(int B, int T, int C, int G, int K,
+                                                     const float* __restrict__ h, void* __restrict__ out) {
+  const int Cg = C / G, TP = T + K, pad = K / 2;
+  const size_t n = (size_t)B * G * TP * Cg;
+  for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)gridDim.x * NT) {
+    const int c = (int)(i % Cg);
+    size_t r = i / Cg;
+    const int tp = (int)(r % TP);
+    r /= TP;
+    const int g = (int)(r % G), b = (int)(r / G);
+    const int t = tp - pad;
+    const float v = (t >= 0 && t < T) ? h[((size_t)b * T + t) * C + (size_t)g * Cg + c] : 0.f;
+    if constexpr (OUT_BF16) static_cast<short*>(out)[i] = f2bf(v);
+    else static_cast<float*>(out)[i] = v;
+  }
+}
+
+// ------------------------------------------------------------------ attention
+// One wave per 16 queries of one (utterance, head); no LDS.  Transposed products keep everything
+// lane-local: S^T = K Q^T puts a query in a lane column (C layout: col = lane & 15 = the query,
+// row = 4 (lane >> 4) + r = the key), so the online max / sum of a query is an in-register fold
+// plus two lane exchanges (xor 16, 32), and the probabilities of the four keys a lane holds are
+// already a B-operand slice of O^T = V^T P^T once the keys of the product's K dimension are taken
+// in the order the lanes hold them (V^T's rows are read in the same order).
+template <bool IN_BF16> struct QkvT;
+template <> struct QkvT<true> { typedef short T; };
+template <> struct QkvT<false> { typedef float T; };
+
+__device__ __forceinline__ float ld_f(const short* p) { return bf2f(*p); }
+__device__ __forceinline__ float ld_f(const float* p) { return *p; }
+
+template <int D, bool F32MATH, bool IN_BF16, bool OUT_BF16>
+__global__ __launch_bounds__(NT) void attention_kernel(int T, int H, const void* __restrict__ qkv_,
+                                                       float scale, void* __restrict__ out_) {
+  typedef typename QkvT<IN_BF16>::T ET;
+  const ET* qkv = static_cast<const ET*>(qkv_);
+  const int lane = threadIdx.x & 63, col = lane & 15, g = lane >> 4;
+  const int q0 = (blockIdx.x * (NT / 64) + (threadIdx.x >> 6)) * 16;
+  if (q0 >= T) return;
+  const int h = blockIdx.y, b = blockIdx.z;
+  const size_t ld = (size_t)3 * H * D;
+  const ET* base = qkv + (size_t)b * T * ld + (size_t)h * D;
+  const ET* Kb = base + (size_t)H * D;
+  const ET* Vb = base + (size_t)2 * H * D;
+  const int qi = q0 + col, qc = qi < T ? qi : T - 1;
+  constexpr int DB = D / 16;
+  f32x4 acc[DB];
+#pragma unroll
+  for (int i = 0; i < DB; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, lsum = 0.f;
+
+  // the query operand (B of S^T = K Q^T), kept for the whole key loop
+  constexpr int NQ = F32MATH ? D / 4 : D / 32;
+  float qf[F32MATH ? NQ : 1];
+  bf16x8 qb[F32MATH ? 1 : NQ];
+  if constexpr (F32MATH) {
+#pragma unroll
+    for (int c = 0; c < NQ; ++c) qf[c] = ld_f(base + (size_t)qc * ld + 4 * c + g);
+  } else {
+#pragma unroll
+    for (int c = 0; c < NQ; ++c)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) qb[c][j] = f2bf(ld_f(base + (size_t)qc * ld + 32 * c + 8 * g + j));
+  }
+
+  for (int kt = 0; kt < T; kt += 32) {
+    f32x4 s[2];
+#pragma unroll
+    for (int blk = 0; blk < 2; ++blk) {
+      s[blk] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const int kk = kt + 16 * blk + col, kc = kk < T ? kk : T - 1;
+      const ET* kr = Kb + (size_t)kc * ld;
+      if constexpr (F32MATH) {
+#pragma unroll
+        for (int c = 0; c < NQ; ++c)
+          s[blk] = __builtin_amdgcn_mfma_f32_16x16x4f32(ld_f(kr + 4 * c + g), qf[c], s[blk], 0, 0, 0);
+      } else {
+#pragma unroll
+        for (int c = 0; c < NQ; ++c) {
+          bf16x8 kf;
+          if constexpr (IN_BF16) {
+            kf = *reinterpret_cast<const bf16x8*>(kr + 32 * c + 8 * g);
+          } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) kf[j] = f2bf(ld_f(kr + 32 * c + 8 * g + j));
+          }
+          s[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qb[c], s[blk], 0, 0, 0);
+        }
+      }
+    }
+    // mask the keys past T, fold the tile into the running max / sum
+    float mx = -INFINITY;
+#pragma unroll
+    for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = kt + 16 * blk + 4 * g + r;
+        const float v = key < T ? s[blk][r] * scale : -INFINITY;
+        s[blk][r] = v;
+        mx = fmaxf(mx, v);
+      }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float mn = fmaxf(m, mx);  // finite: key kt < T is in every tile
+    const float resc = expf(m - mn);  // 0 on the first tile (m = -inf)
+    float ps = 0.f;
+#pragma unroll
+    for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float p = expf(s[blk][r] - mn);  // exp(-inf) = 0 for a masked key
+        s[blk][r] = p;
+        ps += p;
+      }
+    ps += __shfl_xor(ps, 16, 64);
+    ps += __shfl_xor(ps, 32, 64);
+    lsum = lsum * resc + ps;
+    m = mn;
+#pragma unroll
+    for (int i = 0; i < DB; ++i) acc[i] *= resc;
+
+    // O^T += V^T P^T over the tile's 32 keys, in the lanes' key order
+    if constexpr (F32MATH) {
+#pragma unroll
+      for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int key = kt + 16 * blk + 4 * g + r, kc = key < T ? key : T - 1;
+          const ET* vr = Vb + (size_t)kc * ld;
+#pragma unroll
+          for (int i = 0; i < DB; ++i)
+            acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(ld_f(vr + 16 * i + col), s[blk][r], acc[i], 0, 0, 0);
+        }
+    } else {
+      bf16x8 pf;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) pf[j] = f2bf(s[j >> 2][j & 3]);
+#pragma unroll
+      for (int i = 0; i < DB; ++i) {
+        bf16x8 vf;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int key = kt + 16 * (j >> 2) + 4 * g + (j & 3), kc = key < T ? key : T - 1;
+          vf[j] = f2bf(ld_f(Vb + (size_t)kc * ld + 16 * i + col));
+        }
+        acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, acc[i], 0, 0, 0);
+      }
+    }
+  }
+  if (qi < T) {
+    const float inv = 1.f / lsum;
+    const size_t o = ((size_t)b * T + qi) * ((size_t)H * D) + (size_t)h * D;
+#pragma unroll
+    for (int i = 0; i < DB; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float y = acc[i][r] * inv;
+        const size_t e = o + 16 * i + 4 * g + r;
+        if constexpr (OUT_BF16) static_cast<short*>(out_)[e] = f2bf(y);
+        else static_cast<float*>(out_)[e] = y;
+      }
+  }
+}
+
+template <int D>
+void launch_attention(dim3 grid, hipStream_t st, int T, int H, const void* qkv, int in_bf16, int f32math,
+                      float scale, void* out, int out_bf16) {
+  if (f32math) {
+    if (in_bf16) {
+      if (out_bf16) attention_kernel<D, true, true, true><<<grid, NT, 0, st>>>(T, H, qkv, scale, out);
+      else attention_kernel<D, true, true, false><<<grid, NT, 0, st>>>(T, H, qkv, scale, out);
+    } else {
+      if (out_bf16) attention_kernel<D, true, false, true><<<grid, NT, 0, st>>>(T, H, qkv, scale, out);
+      else attention_kernel<D, true, false, false><<<grid, NT, 0, st>>>(T, H, qkv, scale, out);
+    }
+  } else {
+    if (in_bf16) {
+      if (out_bf16) attention_kernel<D, false, true, true><<<grid, NT, 0, st>>>(T, H, qkv, scale, out);
+      else attention_kernel<D, false, true, false><<<grid, NT, 0, st>>>(T, H, qkv, scale, out);
+    } else {
+      if (out_bf16) attention_kernel<D, false, false, true><<<grid, NT, 0, st>>>(T, H, qkv, scale, out);
+      else attention_kernel<D, false, false, false><<<grid, NT, 0, st>>>(T, H, qkv, scale, out);
+    }
+  }
+}
+
+unsigned stream_grid(size_t n) {
+  size_t g = (n + NT - 1) / NT;
+  if (g > 4096) g = 4096;
+  if (g < 1) g = 1;
+  return (unsigned)g;
+}
+
+}  // namespace
+
+extern "C" size_t mlvae_w2v_stats_workspace_size(size_t n) {
+  return (size_t)stats_blocks(n) * 2 * sizeof(double);
+}
+
+extern "C" int mlvae_w2v_tensor_stats(size_t n, const float* x, float eps, float* stats, void* ws,
+                                      size_t ws_bytes, void* stream) {
+  if (n == 0 || !x || !stats || !ws || ((uintptr_t)ws % 8) || ws_bytes < mlvae_w2v_stats_workspace_size(n)) {
+    mlvae_set_error("w2v_tensor_stats: n=%zu needs x, stats and an 8-byte aligned workspace of %zu bytes", n,
+                    mlvae_w2v_stats_workspace_size(n));
+    return 1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = stats_blocks(n);
+  stats_partial<<<nb, NT, 0, st>>>(n, x, static_cast<double*>(ws));
+  stats_final<<<1, NT, 0, st>>>(n, nb, static_cast<const double*>(ws), eps, stats);
+  MLVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int mlvae_w2v_scale_shift(size_t n, const float* x, const float* stats, float* out, void* stream) {
+  if (!x || !stats || !out) { mlvae_set_error("w2v_scale_shift: null pointer"); return 1; }
+  if (n == 0) return 0;
+  scale_shift_kernel<<<stream_grid(n), NT, 0, (hipStream_t)stream>>>(n, x, stats, out);
+  MLVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int mlvae_w2v_conv0_supported(int C, int K) { return C >= 1 && C <= 512 && K >= 1 && K <= CONV0_KMAX; }
+
+extern "C" int mlvae_w2v_conv0(int B, int N, int T0, int C, int K, int stride, const float* wav,
+                               const float* stats, const float* w, const float* bias, const float* gamma,
+                               const float* beta, float eps, void* out, int out_bf16, void* stream) {
+  if (!mlvae_w2v_conv0_supported(C, K) || B < 1 || stride < 1 || T0 < 1 || N < K ||
+      (long long)(T0 - 1) * stride + K > N || !wav || !w || !bias || !gamma || !beta || !out) {
+    mlvae_set_error("w2v_conv0: B=%d N=%d T0=%d C=%d K=%d stride=%d unsupported (C <= 512, K <= %d, "
+                    "(T0 - 1) stride + K <= N)", B, N, T0, C, K, stride, CONV0_KMAX);
+    return 1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const long long frames = (long long)B * T0;
+  const long long waves = (frames + CONV0_FRAMES - 1) / CONV0_FRAMES;
+  const unsigned grid = (unsigned)((waves + NT / 64 - 1) / (NT / 64));
+#define W2V_CONV0(CPL)                                                                                      \
+  do {                                                                                                      \
+    if (out_bf16) conv0_kernel<CPL, true><<<grid, NT, 0, st>>>(B, N, T0, C, K, stride, wav, stats, w, bias, \
+                                                                gamma, beta, eps, out);                     \
+    else conv0_kernel<CPL, false><<<grid, NT, 0, st>>>(B, N, T0, C, K, stride, wav, stats, w, bias, gamma,  \
+                                                       beta, eps, out);                                     \
+  } while (0)
+  if (C <= 64) W2V_CONV0(1);
+  else if (C <= 128) W2V_CONV0(2);
+  else if (C <= 256) W2V_CONV0(4);
+  else W2V_CONV0(8);
+#undef W2V_CONV0
+  MLVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int mlvae_w2v_rows(int N, int C, const float* x, int ldx, const float* bias, const float* gamma,
+                              const float* beta, float eps, int gelu, const float* res, int ldres,
+                              float* out_f32, void* out_bf16, int ldo, void* stream) {
+  const bool ln = gamma != nullptr;
+  if (N < 0 || C < 4 || C % 4 || !x || ldx < C || ldo < C || (res && ldres < C) || (!out_f32 && !out_bf16) ||
+      (ln && (!beta || C > 256 * ROWS_MAX_LN))) {
+    mlvae_set_error("w2v_rows: N=%d C=%d ldx=%d ldo=%d unsupported (C %% 4 == 0, LN needs gamma and beta, "
+                    "C <= %d)", N, C, ldx, ldo, 256 * ROWS_MAX_LN);
+    return 1;
+  }
+  // 16-byte accesses: aligned rows (8 bytes for the bf16 output)
+  if ((ldx % 4) || (ldo % 4) || (res && (ldres % 4)) || ((uintptr_t)out_bf16 % 8) ||
+      (((uintptr_t)x | (uintptr_t)bias | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)res |
+        (uintptr_t)out_f32) % 16)) {
+    mlvae_set_error("w2v_rows: buffers must be 16-byte aligned and the leading dimensions multiples of 4");
+    return 1;
+  }
+  if (N == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = (unsigned)(((long long)N + NT / 64 - 1) / (NT / 64));
+  if (ln) rows_kernel<true><<<grid, NT, 0, st>>>(N, C, x, ldx, bias, gamma, beta, eps, gelu, res, ldres, out_f32,
+                                                 static_cast<short*>(out_bf16), ldo);
+  else rows_kernel<false><<<grid, NT, 0, st>>>(N, C, x, ldx, bias, gamma, beta, eps, gelu, res, ldres, out_f32,
+                                               static_cast<short*>(out_bf16), ldo);
+  MLVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int mlvae_w2v_regroup(int B, int T, int C, int G, int K, const float* h, void* out, int out_bf16,
+                                 void* stream) {
+  if (B < 1 || T < 1 || C < 1 || G < 1 || K < 1 || C % G || !h || !out) {
+    mlvae_set_error("w2v_regroup: B=%d T=%d C=%d G=%d K=%d unsupported (C %% G == 0)", B, T, C, G, K);
+    return 1;
+  }
+  const size_t n = (size_t)B * (T + K) * C;
+  hipStream_t st = (hipStream_t)stream;
+  if (out_bf16) regroup_kernel<true><<<stream_grid(n), NT, 0, st>>>(B, T, C, G, K, h, out);
+  else regroup_kernel<false><<<stream_grid(n), NT, 0, st>>>(B, T, C, G, K, h, out);
+  MLVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int mlvae_w2v_attention_supported(int T, int H, int d) {
+  return T >= 1 && H >= 1 && H <= 65535 && (d == 32 || d == 64);
+}
+
+extern "C" int mlvae_w2v_attention(int B, int T, int H, int d, const void* qkv, int qkv_bf16, int f32_math,
+                                   float scale, void* out, int out_bf16, void* stream) {
+  if (!mlvae_w2v_attention_supported(T, H, d) || B < 1 || B > 65535 || !qkv || !out ||
+      (qkv_bf16 && ((uintptr_t)qkv % 16))) {
+    mlvae_set_error("w2v_attention: B=%d T=%d H=%d d=%d unsupported (d in {32, 64}, B, H <= 65535, "
+                    "16-byte aligned bf16 qkv)", B, T, H, d);
+    return 1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  dim3 grid((unsigned)((T + 63) / 64), (unsigned)H, (unsigned)B);
+  if (d == 32) launch_attention<32>(grid, st, T, H, qkv, qkv_bf16, f32_math, scale, out, out_bf16);
+  else launch_attention<64>(grid, st, T, H, qkv, qkv_bf16, f32_math, scale, out, out_bf16);
+  MLVAE_CHECK_LAUNCH();
+  return 0;
+}

@@ -194,6 +194,16 @@ _SIGS = {
     "mlvae_kaldi_fbank": [I, I, P, I, P, I, I, I, I, I, P, P, I, P, P, SZ, P],
     "mlvae_cmvn_accumulate": [I, I, I, I, P, I, P, P, P, P, P],
     "mlvae_cmvn_apply": [I, I, I, I, P, I, P, P, P, P, P],
+    # the frozen wav2vec2 encoder (csrc/w2v.hip)
+    "mlvae_w2v_stats_workspace_size": [SZ],
+    "mlvae_w2v_tensor_stats": [SZ, P, F, P, P, SZ, P],
+    "mlvae_w2v_scale_shift": [SZ, P, P, P, P],
+    "mlvae_w2v_conv0_supported": [I, I],
+    "mlvae_w2v_conv0": [I, I, I, I, I, I, P, P, P, P, P, P, F, P, I, P],
+    "mlvae_w2v_rows": [I, I, P, I, P, P, P, F, I, P, I, P, P, I, P],
+    "mlvae_w2v_regroup": [I, I, I, I, I, P, P, I, P],
+    "mlvae_w2v_attention_supported": [I, I, I],
+    "mlvae_w2v_attention": [I, I, I, I, P, I, I, F, P, I, P],
 }
 _RESTYPE = {
     "mlvae_last_error": C.c_char_p,
@@ -221,6 +231,7 @@ _RESTYPE = {
     "mlvae_fbank_workspace_size": SZ,
     "mlvae_kaldi_fbank_table_size": SZ,
     "mlvae_kaldi_fbank_workspace_size": SZ,
+    "mlvae_w2v_stats_workspace_size": SZ,
 }
 
 _lib = None

@@ -1921,3 +1921,168 @@ def cmvn_apply(feats, frames, spk, stats):
     if B and T:
         _raise_cmvn(err, "cmvn_apply")
     return feats
+
+
+# ---- the frozen wav2vec2 encoder (csrc/w2v.hip); forward only, no autograd
+def _w2v_dev(t, what, dtypes=(torch.float32,)):
+    if not (t.is_cuda and t.dtype in dtypes and t.is_contiguous()):
+        raise TypeError(f"{what}: expected a contiguous HIP tensor of {dtypes}, got {t.dtype} on {t.device} "
+                        "(the HIP path has no CPU fallback)")
+    return t
+
+
+def w2v_tensor_stats(x, eps=1e-5):
+    """[mean, 1 / sqrt(biased var + eps)] over every element of the fp32 tensor x, as a device
+    tensor of two floats (F.layer_norm(x, x.shape)'s statistics; fixed-order sums)."""
+    x = _w2v_dev(x, "w2v_tensor_stats")
+    if x.numel() == 0:
+        raise ValueError("w2v_tensor_stats: empty tensor")
+    stats = torch.empty(2, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        ws = _workspace(lib().mlvae_w2v_stats_workspace_size(x.numel()), "w2v_stats")
+        check(lib().mlvae_w2v_tensor_stats(x.numel(), _p(x), float(eps), _p(stats), _p(ws), ws.numel() * 4,
+                                           _stream()), "w2v_tensor_stats")
+    return stats
+
+
+def w2v_scale_shift(x, stats):
+    """(x - stats[0]) * stats[1], fp32, same shape."""
+    x = _w2v_dev(x, "w2v_scale_shift")
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        check(lib().mlvae_w2v_scale_shift(x.numel(), _p(x), _p(stats), _p(out), _stream()), "w2v_scale_shift")
+    return out
+
+
+def w2v_conv0(wav, stats, w, bias, gamma, beta, stride, eps=1e-5, out_dtype=torch.float32):
+    """[B, T0, C] = GELU(LN_C(conv1d((wav - mean) rstd, w [C, K], stride) + bias)), channels-last;
+    stats None: the waveform as it is."""
+    wav = _w2v_dev(wav, "w2v_conv0 wav")
+    B, N = wav.shape
+    C, K = w.shape
+    if not lib().mlvae_w2v_conv0_supported(C, K):
+        raise ValueError(f"w2v_conv0: C = {C}, K = {K} unsupported (C <= 512, K <= 10)")
+    if N < K:
+        raise ValueError(f"w2v_conv0: {N} samples are shorter than the kernel ({K})")
+    T0 = (N - K) // stride + 1
+    out = torch.empty(B, T0, C, device=wav.device, dtype=out_dtype)
+    with torch.cuda.device(wav.device):
+        check(lib().mlvae_w2v_conv0(B, N, T0, C, K, stride, _p(wav), None if stats is None else _p(stats),
+                                    _p(w), _p(bias), _p(gamma), _p(beta), float(eps), out.data_ptr(),
+                                    int(out_dtype == torch.bfloat16), _stream()), "w2v_conv0")
+    return out
+
+
+def w2v_rows(x, *, bias=None, gamma=None, beta=None, eps=1e-5, gelu=False, res=None, out_f32=False,
+             out_bf16=False):
+    """Per row of the fp32 x [..., C]: y = x + bias; LN_C (gamma given); GELU; + res.  out_f32: False,
+    True (a new tensor) or a tensor to write (res itself: in place); out_bf16: False / True.
+    Returns (fp32 result or None, bf16 result or None)."""
+    x = _w2v_dev(x, "w2v_rows x")
+    C = x.shape[-1]
+    N = x.numel() // C
+    if C % 4 or (gamma is not None and C > 2048):
+        raise ValueError(f"w2v_rows: C = {C} is unsupported (a multiple of 4; LayerNorm over at most 2048)")
+    f32 = torch.empty_like(x) if out_f32 is True else (None if out_f32 is False else out_f32)
+    b16 = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16) if out_bf16 else None
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(x.device):
+        check(lib().mlvae_w2v_rows(N, C, _p(x), C, ptr(bias), ptr(gamma), ptr(beta), float(eps), int(gelu),
+                                   ptr(res), C, ptr(f32), ptr(b16), C, _stream()), "w2v_rows")
+    return f32, b16
+
+
+def w2v_regroup(h, G, K, out_dtype=torch.float32):
+    """h [B, T, C] fp32 -> the zero-padded group-major copy [B, G, T + K, C / G] (frames at rows
+    K/2 .. K/2 + T - 1): a positional-conv window is contiguous in it."""
+    h = _w2v_dev(h, "w2v_regroup h")
+    B, T, C = h.shape
+    out = torch.empty(B, G, T + K, C // G, device=h.device, dtype=out_dtype)
+    with torch.cuda.device(h.device):
+        check(lib().mlvae_w2v_regroup(B, T, C, G, K, _p(h), out.data_ptr(), int(out_dtype == torch.bfloat16),
+                                      _stream()), "w2v_regroup")
+    return out
+
+
+def w2v_attention_supported(T, H, d):
+    return bool(lib().mlvae_w2v_attention_supported(T, H, d))
+
+
+def w2v_attention(qkv, B, T, H, d, *, scale=1.0, f32_math=False, out_dtype=torch.float32):
+    """[B T, H d] = softmax(scale Q K^T) V per (utterance, head) from the fused qkv [B T, 3 H d]
+    (fp32 or bf16), no mask.  An unsupported shape raises: there is no fallback."""
+    qkv = _w2v_dev(qkv, "w2v_attention qkv", (torch.float32, torch.bfloat16))
+    if tuple(qkv.shape) != (B * T, 3 * H * d):
+        raise ValueError(f"w2v_attention: qkv is {tuple(qkv.shape)}, expected {(B * T, 3 * H * d)}")
+    if not w2v_attention_supported(T, H, d) or B > 65535:
+        raise ValueError(f"w2v_attention: B = {B}, T = {T}, H = {H}, d = {d} is unsupported "
+                         "(d in {32, 64}, B and H <= 65535)")
+    out = torch.empty(B * T, H * d, device=qkv.device, dtype=out_dtype)
+    with torch.cuda.device(qkv.device):
+        check(lib().mlvae_w2v_attention(B, T, H, d, qkv.data_ptr(), int(qkv.dtype == torch.bfloat16),
+                                        int(f32_math), float(scale), out.data_ptr(),
+                                        int(out_dtype == torch.bfloat16), _stream()), "w2v_attention")
+    return out
+
+
+def w2v_gemm(A, W, C, M, N, K, lda, ldc, *, bias=None, beta=0.0, batch=1, a_bs=0, b_bs=0, c_bs=0):
+    """C_z [M, N] (fp32, leading dimension ldc) = A_z W_z^T + bias + beta C_z for z < batch, A_z rows
+    of K elements every lda (lda < K: overlapping rows, the conv windows of a channels-last
+    sequence), W_z [N, K]; strides in elements.  bf16 operands: mlvae_gemm_bf16 (one batched launch;
+    a bf16 C is written by its EPI_OUT_BF16 epilogue, beta 0); fp32 operands: mlvae_gemm's exact-fp32
+    path, one launch per z (the parity mode)."""
+    l = lib()
+    c_bf16 = C.dtype == torch.bfloat16
+    if A.dtype != W.dtype or A.dtype not in (torch.float32, torch.bfloat16) or not (
+            C.dtype == torch.float32 or (c_bf16 and A.dtype == torch.bfloat16 and beta == 0.0)):
+        raise TypeError(f"w2v_gemm: operands {A.dtype} / {W.dtype}, C {C.dtype}, beta {beta}")
+    bp = None if bias is None else bias.data_ptr()
+    with torch.cuda.device(A.device):
+        if A.dtype == torch.bfloat16:
+            ws = _workspace(l.mlvae_gemm_bf16_workspace_size(M, N, K, batch))
+            check(l.mlvae_gemm_bf16(0, 1, M, N, K, batch, A.data_ptr(), lda, a_bs, W.data_ptr(), K, b_bs,
+                                    C.data_ptr(), ldc, c_bs, float(beta), bp, None, 32 if c_bf16 else 0, None, 0,
+                                    0, 0, 0, 0, 0, 0.0, _p(ws), ws.numel() * 4, _stream()), "mlvae_gemm_bf16")
+        else:
+            ws = _workspace(l.mlvae_gemm_workspace_size(M, N, K))
+            for z in range(batch):
+                check(l.mlvae_gemm(0, 0, 1, M, N, K, 1.0, A.data_ptr() + 4 * z * a_bs, lda,
+                                   W.data_ptr() + 4 * z * b_bs, K, float(beta), C.data_ptr() + 4 * z * c_bs, ldc,
+                                   bp, None, 0, None, 0, 0, 0, _p(ws), ws.numel() * 4, _stream()), "mlvae_gemm")
+    return C
+
+
+def w2v_linear(x, W, bias=None, out=None, beta=0.0, out_dtype=torch.float32):
+    """out [M, N] = x [M, K] W [N, K]^T + bias + beta out; fp32, or bf16 (bf16 operands, no out)."""
+    M, K = x.shape
+    N = W.shape[0]
+    if out is None:
+        out = torch.empty(M, N, device=x.device, dtype=out_dtype)
+    return w2v_gemm(x, W, out, M, N, K, K, N, bias=bias, beta=beta)
+
+
+def w2v_conv_gemm(x, W, bias, k, stride):
+    """Strided conv1d of the channels-last x [B, T, Cin] as a GEMM over overlapping rows: frame t's
+    window is the k Cin contiguous elements at t stride Cin.  W [Cout, k Cin] (the conv weight
+    permuted to [Cout][k][Cin]).  Returns fp32 [B, Tout, Cout]."""
+    B, T, Cin = x.shape
+    Cout = W.shape[0]
+    if T < k:
+        raise ValueError(f"w2v_conv_gemm: {T} frames are shorter than the kernel ({k})")
+    Tout = (T - k) // stride + 1
+    out = torch.empty(B, Tout, Cout, device=x.device, dtype=torch.float32)
+    return w2v_gemm(x, W, out, Tout, Cout, k * Cin, stride * Cin, Cout, bias=bias, batch=B,
+                    a_bs=T * Cin, c_bs=Tout * Cout)
+
+
+def w2v_pos_conv(hp, W, T, C):
+    """The grouped positional conv on the regrouped hp [B, G, T + K, C / G] (w2v_regroup): per
+    (utterance, group) a GEMM over overlapping rows, M = T (the conv's last frame is dropped),
+    against W [G, C / G, K C / G] (the folded weight regrouped to [G][out][K][in]).  Returns the
+    fp32 conv output [B, T, C] without the bias."""
+    B, G, TP, Cg = hp.shape
+    K = TP - T
+    out = torch.empty(B, T, C, device=hp.device, dtype=torch.float32)
+    for b in range(B):  # the weight's stride follows the group, not the utterance
+        w2v_gemm(hp[b], W, out[b], T, Cg, K * Cg, Cg, C, batch=G, a_bs=TP * Cg, b_bs=Cg * K * Cg, c_bs=Cg)
+    return out

@@ -52,6 +52,7 @@ class SBModel(MDModel):
     dp_exact = True  # data parallel: models/md_model.py's shard-exact step
     noise = None
     _decode_err = None  # the stage's decode error words, OR-ed on the device
+    _phn_out_fc = "phn_recog_fc"  # the module over the recogniser's output in the pi path
 
     # ------------------------------------------------------------------ stages
     def on_stage_start(self, stage, epoch=None):
@@ -109,7 +110,7 @@ class SBModel(MDModel):
     def compute_forward(self, batch, stage):
         predictions, batch, feats, feat_lens, noise = self._upstream(batch)
         if self.target in (Target.VAE, Target.TEST):
-            rnn_out, pi_logits = self._pi_logits(predictions, feats, "phn_recog_fc")
+            rnn_out, pi_logits = self._pi_logits(predictions, feats, self._phn_out_fc)
             sampled_pi = ops.pi_sample(pi_logits, self.modules.training, u=noise.get("pi_u"))
             predictions["sampled_pi"] = sampled_pi
             self._decode_and_nll(predictions, batch, feat_lens, stage)
@@ -145,13 +146,13 @@ class SBModel(MDModel):
         if target in (Target.PHN_RECOG, Target.VAE, Target.TEST):
             seqs, seq_lens = batch["gt_cnncl_seq"]
             phn = run(target == Target.PHN_RECOG, lambda: self.modules["phoneme_recognizer"](
-                feats, feat_lens, seqs, seq_lens, fa_boundary_seqs))
+                self._recog_input(feats), feat_lens, seqs, seq_lens, fa_boundary_seqs))
             predictions["phn_recog_out"] = phn["out"]
             predictions["losses"].update(phn["losses"])
 
         if target in (Target.B_DETECTOR, Target.VAE, Target.TEST):
             bnd = run(target == Target.B_DETECTOR, lambda: self.modules["boundary_detector"](
-                feats, feat_lens, fa_boundary_seqs, uniform_u=noise.get("boundary_u")))
+                self._detector_input(feats), feat_lens, fa_boundary_seqs, uniform_u=noise.get("boundary_u")))
             predictions["boundary_v"] = bnd["boundary_v"]
             predictions["losses"].update(bnd["losses"])
         return predictions, batch, feats, feat_lens, noise
@@ -165,13 +166,24 @@ class SBModel(MDModel):
         feats, feat_lens = batch["feat"]
         return self.hparams.normalizer(feats, feat_lens, epoch=self.hparams.epoch_counter.current), feat_lens
 
+    # what the recogniser, the detector and the pi path read: the input frames themselves; the
+    # wav2vec2 recipes (models/w2v_MD_VAE) put an FC over the encoder's features in each place
+    def _recog_input(self, feats):
+        return feats
+
+    def _detector_input(self, feats):
+        return feats
+
+    def _pi_feats(self, feats):
+        return self.modules["feat_fc"](feats)
+
     def _dp_lens_field(self, batch, stage):
         return self._feat_field()
 
     def _pi_logits(self, predictions, feats, phn_fc):
         """feat_fc + the recogniser output's FC (module name phn_fc) -> concat_fc -> rnn -> pi_fc:
         (rnn_out (B, T, C), pi_logits (B, T, 2))."""
-        feat_fc_out = self.modules["feat_fc"](feats)
+        feat_fc_out = self._pi_feats(feats)
         phn_fc_out = self.modules[phn_fc](predictions["phn_recog_out"].detach())
         rnn_in = self.modules["concat_fc"](torch.cat([feat_fc_out, phn_fc_out], dim=-1))
         rnn_out = self.modules["rnn"](rnn_in)[0]          # (B, T, C)
