@@ -462,6 +462,50 @@ int mlvae_conv1d_dgrad(int B, int T, int Cin, int Cout, int K, const float* dy, 
 size_t mlvae_conv1d_wgrad_workspace_size(int B, int T, int Cin, int Cout, int K);
 int mlvae_conv1d_wgrad(int B, int T, int Cin, int Cout, int K, const float* dy, int lddy, const float* x,
                        int ldx, float* dw, float* db, void* ws, size_t ws_bytes, void* stream);
+/* The CRDNN's convolutional front end (csrc/conv2d.hip): the Conv2d / LayerNorm / pooling blocks
+ * the CRDNN_CTC recipes' yaml asks of SpeechBrain's CRDNN lobe (ref:src/models/CRDNN_CTC/model.yaml:23-35).
+ * Activations channels-last [B][T][F][C], contiguous fp32, 16-byte aligned; no utterance lengths
+ * (the convolution runs over the padded batch).
+ *   conv2d: 3x3, stride 1, "same", reflect padding 1 on T and F (x[-1] = x[1], x[T] = x[T-2]);
+ *     w torch layout [Cout][Cin][3 (time)][3 (freq)] fp32; bf16 MFMA operands, fp32 accumulate.
+ *     fwd:   y = conv(x) + bias          dgrad: dx = conv^T(dy) (border rows folded onto their sources)
+ *     wgrad: dw, db (db optional) overwritten; deterministic (fixed-order sums, no atomics)
+ *     Limits: Cin, Cout multiples of 16 in [16, 256] (mlvae_conv2d_supported), T >= 2, F >= 2.
+ *     workspace_size(op, ...): op 0 = fwd, 1 = dgrad, 2 = wgrad.
+ *   conv2d_first: the Cin = 1 layer on x [B][T][F]: direct fp32 kernels, forward and weight + bias
+ *     gradient (w [Cout][1][3][3]); Cout a multiple of 16 up to 256.
+ *   ln_fc_act: y = LeakyReLU_0.01(LayerNorm_(F,C)(x) * gamma + beta), one row per (b, t), rows =
+ *     B T, gamma / beta [F][C], biased variance; mean / rstd [rows] saved.  pool = 1: then the
+ *     frequency max-pool 2 (stride 2, floor: y [rows][F/2][C]; a tie keeps the lower bin) and the
+ *     Dropout2d factor keep [B][F/2] (0 or 1/(1-p); NULL = none; b = row / T).  bwd: dx, dgamma,
+ *     dbeta (overwritten, deterministic) from dy, the saved x, mean, rstd.  C % 4 == 0.
+ *   time_pool: max over frame pairs, y [B][T/2][D] of x [B][T][D] (floor; D % 4 == 0); bwd routes
+ *     dy to the pair's maximum (a tie: the earlier frame). */
+int mlvae_conv2d_supported(int Cin, int Cout);
+size_t mlvae_conv2d_workspace_size(int op, int B, int T, int F, int Cin, int Cout);
+int mlvae_conv2d_fwd(int B, int T, int F, int Cin, int Cout, const float* x, const float* w, const float* bias,
+                     float* y, void* ws, size_t ws_bytes, void* stream);
+int mlvae_conv2d_dgrad(int B, int T, int F, int Cin, int Cout, const float* dy, const float* w, float* dx,
+                       void* ws, size_t ws_bytes, void* stream);
+int mlvae_conv2d_wgrad(int B, int T, int F, int Cin, int Cout, const float* dy, const float* x, float* dw,
+                       float* db, void* ws, size_t ws_bytes, void* stream);
+/* the forward's first launch alone: xp = the reflect-padded bf16 copy [B][T+2][F+2][C] of x */
+int mlvae_conv2d_pad_bf16(int B, int T, int F, int C, const float* x, void* xp, void* stream);
+int mlvae_conv2d_first_fwd(int B, int T, int F, int Cout, const float* x, const float* w, const float* bias,
+                           float* y, void* stream);
+size_t mlvae_conv2d_first_wgrad_workspace_size(int B, int T, int F, int Cout);
+int mlvae_conv2d_first_wgrad(int B, int T, int F, int Cout, const float* dy, const float* x, float* dw,
+                             float* db, void* ws, size_t ws_bytes, void* stream);
+int mlvae_ln_fc_act_fwd(long long rows, int T, int F, int C, const float* x, const float* gamma,
+                        const float* beta, const float* keep, int pool, float eps, float* y, float* mean,
+                        float* rstd, void* stream);
+size_t mlvae_ln_fc_act_bwd_workspace_size(long long rows, int F, int C);
+int mlvae_ln_fc_act_bwd(long long rows, int T, int F, int C, const float* dy, const float* x,
+                        const float* gamma, const float* beta, const float* keep, int pool, const float* mean,
+                        const float* rstd, float* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
+                        void* stream);
+int mlvae_time_pool_fwd(int B, int T, int D, const float* x, float* y, void* stream);
+int mlvae_time_pool_bwd(int B, int T, int D, const float* dy, const float* x, float* dx, void* stream);
 /* ELBO: reparameterise + KL (ref:src/modules/vanilla_vae.py:37-45) with masked partial
  * sums; ml = [mu | log_var] rows of width 2Z (leading dim ldml). */
 int mlvae_elbo_partials_count(int B, int T, int C);

@@ -59,6 +59,21 @@ _SIGS = {
     "mlvae_conv1d_dgrad": [I, I, I, I, I, P, I, P, P, I, P, I, P],
     "mlvae_conv1d_wgrad_workspace_size": [I, I, I, I, I],
     "mlvae_conv1d_wgrad": [I, I, I, I, I, P, I, P, I, P, P, P, SZ, P],
+    # the CRDNN's convolutional front end (csrc/conv2d.hip)
+    "mlvae_conv2d_supported": [I, I],
+    "mlvae_conv2d_workspace_size": [I, I, I, I, I, I],
+    "mlvae_conv2d_fwd": [I, I, I, I, I, P, P, P, P, P, SZ, P],
+    "mlvae_conv2d_dgrad": [I, I, I, I, I, P, P, P, P, SZ, P],
+    "mlvae_conv2d_wgrad": [I, I, I, I, I, P, P, P, P, P, SZ, P],
+    "mlvae_conv2d_pad_bf16": [I, I, I, I, P, P, P],
+    "mlvae_conv2d_first_fwd": [I, I, I, I, P, P, P, P, P],
+    "mlvae_conv2d_first_wgrad_workspace_size": [I, I, I, I],
+    "mlvae_conv2d_first_wgrad": [I, I, I, I, P, P, P, P, P, SZ, P],
+    "mlvae_ln_fc_act_fwd": [C.c_longlong, I, I, I, P, P, P, P, I, F, P, P, P, P],
+    "mlvae_ln_fc_act_bwd_workspace_size": [C.c_longlong, I, I],
+    "mlvae_ln_fc_act_bwd": [C.c_longlong, I, I, I, P, P, P, P, P, I, P, P, P, P, P, P, SZ, P],
+    "mlvae_time_pool_fwd": [I, I, I, P, P, P],
+    "mlvae_time_pool_bwd": [I, I, I, P, P, P, P],
     "mlvae_boundary_fwd": [SZ, P, P, P, P, U64, U64, P, P, P, P],
     "mlvae_boundary_bwd": [SZ, P, P, P, P, U64, U64, P, P, P, P, P, P],
     "mlvae_pi_sample": [SZ, P, P, U64, U64, I, P, P],
@@ -208,6 +223,9 @@ _SIGS = {
 _RESTYPE = {
     "mlvae_last_error": C.c_char_p,
     "mlvae_conv1d_wgrad_workspace_size": SZ,
+    "mlvae_conv2d_workspace_size": SZ,
+    "mlvae_conv2d_first_wgrad_workspace_size": SZ,
+    "mlvae_ln_fc_act_bwd_workspace_size": SZ,
     "mlvae_skinny_dzw_workspace_size": SZ,
     "mlvae_fp8_scale_workspace_size": SZ,
     "mlvae_gemm_fp8_tn_workspace_size": SZ,

@@ -16,7 +16,7 @@ OUT = os.path.join(HERE, "libmlvae.so")
 # variants, csrc/lstm_common.h) -> libmlvae_diag.so, loaded by the tools through MLVAE_LIB_PATH
 DIAG_OUT = os.path.join(HERE, "libmlvae_diag.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["capi.cpp", "gemm.hip", "gemm_bf16.hip", "gemm_fast.hip", "heads.hip", "skinny.hip", "encoder.hip", "lstm.hip", "lstm_wide.hip", "elbo.hip", "gmm.hip", "hvae.hip", "md.hip", "pi.hip", "flvl.hip", "score.hip", "decode.hip", "align.hip", "ctc_eval.hip", "fbank.hip", "kaldi_fbank.hip", "w2v.hip", "conv.hip", "fp8.hip", "norm.hip", "optim.hip"]
+SOURCES = ["capi.cpp", "gemm.hip", "gemm_bf16.hip", "gemm_fast.hip", "heads.hip", "skinny.hip", "encoder.hip", "lstm.hip", "lstm_wide.hip", "elbo.hip", "gmm.hip", "hvae.hip", "md.hip", "pi.hip", "flvl.hip", "score.hip", "decode.hip", "align.hip", "ctc_eval.hip", "fbank.hip", "kaldi_fbank.hip", "w2v.hip", "conv.hip", "conv2d.hip", "fp8.hip", "norm.hip", "optim.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-I" + CSRC]
 

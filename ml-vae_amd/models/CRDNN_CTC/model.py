@@ -1,11 +1,15 @@
 """The CRDNN_CTC recipe (semantics of ref:src/models/CRDNN_CTC/model.py:22-176): the supervised
-recogniser baseline.  A CRDNN (modules/crdnn.py: here a bidirectional LSTM stack and a DNN) and a
+recogniser baseline.  A CRDNN (modules/crdnn.py: a bidirectional LSTM stack and a DNN; with
+model_cnn.yaml the lobe's CNN front end and time pooling before them, ConvCRDNN) and a
 Linear to ``output_neurons`` classes under a log-softmax, trained by CTC on the pronounced
 phonemes (gt_phn_seq); on every batch of every stage the greedy decode is aligned by edit
 distance to the pronounced and to the canonical sequence (phn_per / cnncl_per), every position
 where the aligned prediction differs from the canonical phoneme is called a mispronunciation
 (plvl_md.*, with correct_per / misp_per), and a Viterbi pass of the CTC chain over the canonical
-sequence gives the phoneme boundaries (boundary.*, and the soft plvl_md scores).
+sequence gives the phoneme boundaries (boundary.*, and the soft plvl_md scores).  With time pooling
+the log-posteriors have T // 2 frames: the relative lengths carry over (the kernels take them
+against pout's own frames), and for the Viterbi pass pout is first resampled to the features'
+frames as the reference's resample_tensor does (resample_frames below).
 
 Kept from the reference: the normaliser is applied; the loss is F.ctc_loss(reduction='mean',
 zero_infinity=True) on the log-posteriors (the mean over the batch of nll_i / U_i), blank =
@@ -35,6 +39,27 @@ from utils.metric_stats.error_rate_stats import ErrorRateStats
 from utils.metric_stats.md_metric_stats import MDMetricStats
 
 logger = logging.getLogger(__name__)
+
+
+def resample_frames(pout, T):
+    """pout [B, T', C] on T frames, as the reference's resample_tensor (ref:src/utils/data_utils.py:107-156):
+    every frame repeated T // T' times, then cut or zero-padded to T (a difference of more than 3
+    frames raises).  T' == T: pout itself."""
+    Tp = pout.shape[1]
+    if Tp == T:
+        return pout
+    factor = T // Tp
+    if factor < 1:
+        raise ValueError(f"resample_frames: non-positive factor for lengths {Tp} and {T}")
+    out = torch.repeat_interleave(pout, factor, dim=1)
+    diff = out.shape[1] - T
+    if abs(diff) > 3:
+        raise ValueError(f"resample_frames: {Tp} frames x {factor} differ from {T} by {diff} (> 3)")
+    if diff > 0:
+        out = out[:, :T]
+    elif diff < 0:
+        out = torch.cat([out, out.new_zeros(out.shape[0], -diff, out.shape[2])], dim=1)
+    return out.contiguous()
 
 
 class SBModel(MDModel):
@@ -74,7 +99,7 @@ class SBModel(MDModel):
         feats, feat_lens = self._normalised_feats(batch, stage)
         out = self.modules["crdnn"](feats)
         out = self.modules["output"](out)
-        return {"pout": ops.log_softmax(out), "pout_lens": feat_lens}
+        return {"pout": ops.log_softmax(out), "pout_lens": feat_lens, "feat_frames": feats.shape[1]}
 
     def _targets(self, batch, key):
         seqs, lens = batch[key]
@@ -103,7 +128,9 @@ class SBModel(MDModel):
             pred, pred_len = ops.ctc_greedy_decode(pout, lens, self._blank())
             ali, edits = ops.edit_align(pred, pred_len, phns, phn_lens, cnncls, cnncl_lens)
             counts = ops.ctc_md_counts(ali, phns, phn_lens, cnncls, cnncl_lens)
-            _, boundary, infeasible = ops.ctc_viterbi(pout, lens, cnncls, cnncl_lens, self._blank())
+            # the boundaries are scored on the features' frames: a time-pooled pout is resampled first
+            pout_t = resample_frames(pout, predictions.get("feat_frames", pout.shape[1]))
+            _, boundary, infeasible = ops.ctc_viterbi(pout_t, lens, cnncls, cnncl_lens, self._blank())
             self._eval_ran = True
             n_inf = infeasible.sum()
             self.infeasible = n_inf if self.infeasible is None else self.infeasible + n_inf
