@@ -162,8 +162,13 @@ __global__ __launch_bounds__(256) void finalize_kernel(const float* pk, int nk, 
   out[0] = kld;
   out[1] = rec;
   float tot = 0.f;  // ref:src/models/md_model.py:191-202 accumulates in dict order (kld, recon)
-  tot = tot + w_kl * kld;
-  tot = tot + w_rec * rec;
+  {
+    // `loss += weight * value` rounds each product to fp32 before it is added: no fused
+    // multiply-add here (it moved the total by an ulp, tests/test_gpu_elbo_kernels.py)
+#pragma clang fp contract(off)
+    tot = tot + w_kl * kld;
+    tot = tot + w_rec * rec;
+  }
   out[2] = tot;
 }
 
