@@ -1094,6 +1094,42 @@ int mlvae_w2v_attention_supported(int T, int H, int d);
 int mlvae_w2v_attention(int B, int T, int H, int d, const void* qkv, int qkv_bf16, int f32_math,
                         float scale, void* out, int out_bf16, void* stream);
 
+/* ---- The wav2vec2 encoder's backward (csrc/w2v.hip; DESIGN.md section 4, "The wav2vec2 encoder",
+ * "Backward").  What fine-tuning (SpeechBrain's freeze: False with freeze_feature_extractor: True,
+ * ref:src/models/w2v_LSTM_FC/model.yaml) needs above the conv stack.  The matrix products (every
+ * Linear's dX and dW, the positional conv's input and weight gradients) are mlvae_gemm_bf16 /
+ * mlvae_gemm, bias gradients mlvae_colsum_ex.  Stream-ordered, caller-owned buffers, no atomics, fixed
+ * reduction orders: a rerun is bit-identical.
+ *
+ * attention_train: mlvae_w2v_attention (the same kernel, the same output bits) that also writes the
+ *   per-query log-sum-exp of the scaled logits, lse [B, H, T] fp32.
+ * attention_bwd: dqkv [B T, 3 H d] from qkv, dout [B T, H d] and lse; bf16 = 1: qkv, dout and dqkv are
+ *   bf16, 0: fp32.  delta [B, H, T] fp32 is scratch: D = rowsum(dout o out), once per query, summed
+ *   as sum_k P dP from the recomputed probabilities (with a stored bf16 `out` the row sums of dS miss
+ *   zero at 2^-9 of their terms; the stored output is therefore not read).  Then two passes: a wave
+ *   owns 16 queries and streams the keys (dQ), a wave owns 16 keys and streams the queries (dK, dV);
+ *   P is recomputed as exp(scale S - lse).  f32_math as the forward.  dQ and dK
+ *   carry `scale`; 1/sqrt(d) folded into the Q rows of a fused weight is the caller's to apply to
+ *   those rows' gradients.
+ * rows_bwd: the backward of mlvae_w2v_rows through y = [GELU] [LN] (x [+ bias]) (contiguous rows of C):
+ *   out = [acc +] dx as fp32 and / or bf16 (acc may be out_f32: the residual stream's gradient
+ *   accumulated in place).  LN (gamma != NULL): dgamma [C], dbeta [C] from per-wave partial rows in ws
+ *   (rows_bwd_workspace_size bytes) folded in wave order.  x may be NULL when there is neither LN nor GELU.
+ * norm_bwd: dx = stats[1] (dy - mean(dy) - xhat mean(dy xhat)) over all n elements, xhat the whole-tensor
+ *   norm's OUTPUT and stats its tensor_stats; the two sums as fp64 partials per workgroup in ws
+ *   (norm_bwd_workspace_size bytes, 8-byte aligned), folded in a fixed order. */
+int mlvae_w2v_attention_train(int B, int T, int H, int d, const void* qkv, int qkv_bf16, int f32_math,
+                              float scale, void* out, int out_bf16, float* lse, void* stream);
+int mlvae_w2v_attention_bwd(int B, int T, int H, int d, const void* qkv, const void* dout, int bf16,
+                            int f32_math, float scale, const float* lse, float* delta, void* dqkv, void* stream);
+size_t mlvae_w2v_rows_bwd_workspace_size(int N, int C);
+int mlvae_w2v_rows_bwd(int N, int C, const float* dy, const float* x, const float* bias, const float* gamma,
+                       const float* beta, float eps, int gelu, const float* acc, float* out_f32,
+                       void* out_bf16, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream);
+size_t mlvae_w2v_norm_bwd_workspace_size(size_t n);
+int mlvae_w2v_norm_bwd(size_t n, const float* dy, const float* xhat, const float* stats, float* dx, void* ws,
+                       size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,13 @@ _SIGS = {
     "mlvae_w2v_regroup": [I, I, I, I, I, P, P, I, P],
     "mlvae_w2v_attention_supported": [I, I, I],
     "mlvae_w2v_attention": [I, I, I, I, P, I, I, F, P, I, P],
+    # its backward
+    "mlvae_w2v_attention_train": [I, I, I, I, P, I, I, F, P, I, P, P],
+    "mlvae_w2v_attention_bwd": [I, I, I, I, P, P, I, I, F, P, P, P, P],
+    "mlvae_w2v_rows_bwd_workspace_size": [I, I],
+    "mlvae_w2v_rows_bwd": [I, I, P, P, P, P, P, F, I, P, P, P, P, P, P, SZ, P],
+    "mlvae_w2v_norm_bwd_workspace_size": [SZ],
+    "mlvae_w2v_norm_bwd": [SZ, P, P, P, P, P, SZ, P],
 }
 _RESTYPE = {
     "mlvae_last_error": C.c_char_p,
@@ -250,6 +257,8 @@ _RESTYPE = {
     "mlvae_kaldi_fbank_table_size": SZ,
     "mlvae_kaldi_fbank_workspace_size": SZ,
     "mlvae_w2v_stats_workspace_size": SZ,
+    "mlvae_w2v_rows_bwd_workspace_size": SZ,
+    "mlvae_w2v_norm_bwd_workspace_size": SZ,
 }
 
 _lib = None

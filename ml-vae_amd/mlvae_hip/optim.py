@@ -116,6 +116,9 @@ class Adam(torch.optim.Optimizer):
                                     p.numel(), _p(self._zero), 1, None, _p(self._step_ctr), None,
                                     float(group["lr"]), float(b1), float(b2), float(group["eps"]),
                                     math.inf, None, _p(hyp), adv, _stream()), "adam_step")
+            # the kernel wrote p behind autograd's back: bump its version counter, as an in-place torch
+            # update would (modules that keep kernel-side copies of their weights refresh by it)
+            torch.autograd.graph.increment_version(p)
             st["step"] = self._step_ctr
         return loss
 

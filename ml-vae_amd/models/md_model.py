@@ -210,7 +210,10 @@ class MDModel(Brain):
                         params = [p for m in info["modules"] for p in self.modules[m].parameters()]
                     else:
                         params = self.modules.parameters()
-                    opt = info["opt_class"](params)
+                    cls = info["opt_class"]
+                    if isinstance(cls, functools.partial) and cls.func is torch.optim.Adam:
+                        cls = functools.partial(hip_optim.Adam, *cls.args, **cls.keywords)
+                    opt = cls(params)
                 else:
                     if isinstance(info, functools.partial) and info.func is torch.optim.Adam:
                         info = functools.partial(hip_optim.Adam, *info.args, **info.keywords)

@@ -1,9 +1,11 @@
-"""The frozen wav2vec2 encoder on the HIP kernels: the call surface of SpeechBrain's
-HuggingFaceWav2Vec2 with ``freeze: True`` that the w2v_MD_VAE recipes use
-(ref:src/models/w2v_MD_VAE/model.yaml:11-16, called at ref:src/models/w2v_MD_VAE/model.py:24).
+"""The wav2vec2 encoder on the HIP kernels: the call surface of SpeechBrain's HuggingFaceWav2Vec2
+with ``freeze: True`` that the w2v_MD_VAE recipes use (ref:src/models/w2v_MD_VAE/model.yaml:11-16,
+called at ref:src/models/w2v_MD_VAE/model.py:24), and with ``freeze: False`` plus
+``freeze_feature_extractor: True`` (fine-tuning above a frozen conv stack) as w2v_LSTM_FC uses it
+(ref:src/models/w2v_LSTM_FC/model.yaml).
 
-Forward only, under no_grad: ``forward(wav [B, N]) -> [B, T_w, hidden]``, T_w = (N - 400) // 320 + 1
-at the large-lv60 geometry.  The operations, in order:
+``forward(wav [B, N]) -> [B, T_w, hidden]``, T_w = (N - 400) // 320 + 1 at the large-lv60 geometry;
+frozen: under no_grad.  The operations, in order:
 
 1. ``normalize_wav``: ``F.layer_norm(wav, wav.shape)`` -- over the WHOLE padded batch tensor, zero
    padding and every utterance included, as SpeechBrain 0.5.x does.  The utterances of a batch are
@@ -29,11 +31,22 @@ Casting, permuting and regrouping the weights for the kernels (the weight norm f
 fused with 1 / sqrt(d) in the Q rows, conv weights as [Cout][K][Cin], the positional conv as
 [G][out][K][in]) happens once, on the first call after a load or a move.
 
+Fine-tuning (``freeze=False, freeze_feature_extractor=True``): steps 1-2 run as above under no_grad
+and save nothing; steps 3-7 run through ``ops.W2VHeadFn`` / ``W2VLayerFn`` / ``W2VTailFn`` (the same
+kernels in the same order, so the output's bits equal the frozen module's) and their HIP backward.
+``parameters()`` then yields the fp32 masters of everything from ``feature_projection`` upward
+(``masked_spec_embed`` is unused without masking and stays a frozen tensor); the kernel-side copies
+are rebuilt per tensor group when a master's version counter moved (an optimizer step, a load).
+``freeze=False`` without ``freeze_feature_extractor`` raises: the conv stack has no backward.
+Train-mode regularisation (the dropouts, layerdrop, SpecAugment masking) is not built: non-zero
+values in a config are ignored with one logged warning, and ``train()`` / ``eval()`` compute the same.
+
 ``precision``: 'bf16' (bf16 GEMM and attention operands, fp32 accumulation; the residual stream,
 the other GEMM outputs and every LayerNorm / GELU / softmax stay fp32) or 'fp32' (the parity mode:
 exact-fp32 GEMMs and the fp32 MFMA in attention).
 """
 import json
+import logging
 import math
 import os
 from collections import OrderedDict
@@ -42,6 +55,12 @@ import torch
 from torch import nn
 
 from mlvae_hip import ops
+
+logger = logging.getLogger(__name__)
+
+# the train-mode regularisation of a HuggingFace config: not built (see the module docstring)
+REGULARISATION = ("hidden_dropout", "attention_dropout", "activation_dropout", "feat_proj_dropout", "layerdrop",
+                  "mask_time_prob", "mask_feature_prob")
 
 LARGE_LV60 = dict(
     conv_dim=[512] * 7, conv_kernel=[10, 3, 3, 3, 3, 2, 2], conv_stride=[5, 2, 2, 2, 2, 2, 2], conv_bias=True,
@@ -139,12 +158,13 @@ def _read_state(source):
 
 class Wav2Vec2(nn.Module):
     def __init__(self, source=None, config="large_lv60", output_norm=True, freeze=True, normalize_wav=True,
-                 precision="bf16", save_path=None):
+                 precision="bf16", save_path=None, freeze_feature_extractor=False):
         super().__init__()
         del save_path  # SpeechBrain's download cache: nothing is downloaded here
-        if not freeze:
-            raise NotImplementedError("Wav2Vec2: freeze=False (fine-tuning) is not built: the encoder has no "
-                                      "backward")
+        if not freeze and not freeze_feature_extractor:
+            raise NotImplementedError("Wav2Vec2: freeze=False with freeze_feature_extractor=False is not built: "
+                                      "the convolutional feature extractor has no backward; pass "
+                                      "freeze_feature_extractor=True to fine-tune everything above it")
         if precision not in ("bf16", "fp32"):
             raise ValueError(f"Wav2Vec2: precision must be 'bf16' or 'fp32', got {precision!r}")
         state = None
@@ -159,13 +179,36 @@ class Wav2Vec2(nn.Module):
             state = _read_state(os.fspath(source))
         self.config = resolve_config(config)
         self.output_norm, self.normalize_wav, self.precision = bool(output_norm), bool(normalize_wav), precision
-        self.freeze = True
-        self._w = OrderedDict()   # the frozen weights under HuggingFace's names (fp32, no grad)
+        self.freeze, self.freeze_feature_extractor = bool(freeze), bool(freeze_feature_extractor)
+        # the weights under HuggingFace's names (fp32).  Frozen: plain tensors.  Fine-tuning: the trainable
+        # ones are nn.Parameters, registered under the same names
+        self._w = OrderedDict()
         self._prep = None         # their kernel-side copies: built on the first call, dropped by a load / move
+        if not self.freeze and not isinstance(config, str):
+            on = [k for k in REGULARISATION if config.get(k)]
+            if on:
+                logger.warning("Wav2Vec2: train-mode regularisation is not built; ignoring %s",
+                               ", ".join(f"{k} = {config[k]}" for k in on))
         if state is None:
             self._init_random()
+            self._make_trainable()
         else:
+            self._make_trainable()
             self._load_source(state, source)
+
+    @staticmethod
+    def trainable_key(key):
+        """Whether fine-tuning trains this state-dict key: everything from the projection upward."""
+        return key.startswith(("feature_projection.", "encoder."))
+
+    def _make_trainable(self):
+        if self.freeze:
+            return
+        for key, shape in state_shapes(self.config).items():
+            if self.trainable_key(key):
+                t = self._w[key] if key in self._w else torch.zeros(shape)
+                # HuggingFace's dotted names: what register_parameter refuses and state_dict needs
+                self._parameters[key] = self._w[key] = nn.Parameter(t)
 
     def _load_source(self, state, source):
         """A HuggingFace state dict from disk: the encoder's keys, bare or under the `wav2vec2.`
@@ -176,10 +219,12 @@ class Wav2Vec2(nn.Module):
         state = {k: v for k, v in state.items() if _POS_OLD.get(k, k) in shapes}
         if "masked_spec_embed" not in state:  # absent when the checkpoint's config masks nothing; unused here
             state["masked_spec_embed"] = torch.zeros(shapes["masked_spec_embed"])
-        res = self.load_state_dict(state, strict=False)
-        if res.missing_keys:
-            raise ValueError(f"Wav2Vec2: {source} lacks {len(res.missing_keys)} of the encoder's tensors "
-                             f"(first: {res.missing_keys[0]})")
+        have = {_POS_OLD.get(k, k) for k in state}
+        missing = [k for k in shapes if k not in have]  # (a parameter's placeholder would hide a missing key)
+        if missing:
+            raise ValueError(f"Wav2Vec2: {source} lacks {len(missing)} of the encoder's tensors "
+                             f"(first: {missing[0]})")
+        self.load_state_dict(state, strict=False)
 
     # ------------------------------------------------------------------ weights
     def _init_random(self):
@@ -200,17 +245,19 @@ class Wav2Vec2(nn.Module):
         self._w = OrderedDict((k, self._w[k]) for k in state_shapes(self.config))
 
     def _apply(self, fn, *args, **kwargs):
-        super()._apply(fn, *args, **kwargs)
+        super()._apply(fn, *args, **kwargs)  # the parameters
         for k, t in self._w.items():
+            if k in self._parameters:
+                self._w[k] = self._parameters[k]
+                continue
             t = fn(t)
             self._w[k] = t if t.is_floating_point() and t.dtype == torch.float32 else t.float()
         self._prep = None
         return self
 
     def _save_to_state_dict(self, destination, prefix, keep_vars):
-        super()._save_to_state_dict(destination, prefix, keep_vars)
-        for k, t in self._w.items():
-            destination[prefix + k] = t
+        for k, t in self._w.items():  # HuggingFace's order, parameters included
+            destination[prefix + k] = t if keep_vars else t.detach()
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
                               error_msgs):
@@ -233,44 +280,81 @@ class Wav2Vec2(nn.Module):
             new[key] = t.detach().to(dev, torch.float32).clone()
             seen.add(key)
         for key in shapes:
-            if key in new:
+            if key in new and key in self._parameters:
+                with torch.no_grad():
+                    self._parameters[key].copy_(new[key])
+            elif key in new:
                 self._w[key] = new[key]
             elif key not in self._w or strict:
                 missing_keys.append(prefix + key)
         self._w = OrderedDict((k, self._w[k]) for k in shapes if k in self._w)
         self._prep = None
 
-    def _prepare(self, dev):
-        """The kernel-side weights: cast, permuted and regrouped once."""
-        cfg, w = self.config, self._w
+    def _groups(self):
+        """The kernel-side weights by group: name -> (the state-dict keys it is built from, builder).
+        A group is rebuilt when one of its keys' tensors was replaced or written (version counter)."""
+        cfg = self.config
         wd = torch.bfloat16 if self.precision == "bf16" else torch.float32
-        f = lambda k: w[k].to(dev, torch.float32).contiguous()
-        m = lambda t: t.to(dev, wd).contiguous()
-        ln = lambda p: (f(p + ".weight"), f(p + ".bias"))
-        P = {"conv": [], "layers": []}
-        for i in range(len(cfg["conv_dim"])):
-            p = f"feature_extractor.conv_layers.{i}."
-            cw = f(p + "conv.weight")  # [Cout, Cin, K]
-            W = cw[:, 0, :].contiguous() if i == 0 else m(cw.permute(0, 2, 1).reshape(cw.shape[0], -1))
-            P["conv"].append((W, f(p + "conv.bias")) + ln(p + "layer_norm"))
-        P["proj_ln"] = ln("feature_projection.layer_norm")
-        P["proj"] = (m(f("feature_projection.projection.weight")), f("feature_projection.projection.bias"))
         H, G, K = cfg["hidden_size"], cfg["num_conv_pos_embedding_groups"], cfg["num_conv_pos_embeddings"]
         Cg = H // G
-        pw = fold_pos_conv(f(POS_G), f(POS_V))  # [H, Cg, K], output channel o = g Cg + j
-        P["pos"] = (m(pw.view(G, Cg, Cg, K).permute(0, 1, 3, 2).reshape(G, Cg, K * Cg)), f(_POS + "bias"))
         scale = (H // cfg["num_attention_heads"]) ** -0.5
+        m = lambda t: t.to(wd).contiguous()
+        ln = lambda p: ((p + ".weight", p + ".bias"), lambda w, b: (w, b))
+        lin = lambda p: ((p + ".weight", p + ".bias"), lambda w, b: (m(w), b))
+        out = OrderedDict()
+        for i in range(len(cfg["conv_dim"])):
+            p = f"feature_extractor.conv_layers.{i}."
+            conv = (lambda cw, cb, g, be: (cw[:, 0, :].contiguous(), cb, g, be)) if i == 0 else (
+                lambda cw, cb, g, be: (m(cw.permute(0, 2, 1).reshape(cw.shape[0], -1)), cb, g, be))  # [Cout][K][Cin]
+            out[f"conv{i}"] = ((p + "conv.weight", p + "conv.bias", p + "layer_norm.weight", p + "layer_norm.bias"),
+                               conv)
+        out["proj_ln"] = ln("feature_projection.layer_norm")
+        out["proj"] = lin("feature_projection.projection")
+
+        def pos(g, v, b):  # the folded weight [H, Cg, K], output channel o = g Cg + j, regrouped [G][out][K][in]
+            return m(fold_pos_conv(g, v).view(G, Cg, Cg, K).permute(0, 1, 3, 2).reshape(G, Cg, K * Cg)), b
+
+        out["pos"] = ((POS_G, POS_V, _POS + "bias"), pos)
+        if not self.freeze:  # the input gradient's weight: taps reversed, in / out swapped, [G][in][K][out]
+            out["pos_rev"] = ((POS_G, POS_V), lambda g, v: m(
+                fold_pos_conv(g, v).view(G, Cg, Cg, K).flip(-1).permute(0, 2, 3, 1).reshape(G, Cg, K * Cg)))
         for i in range(cfg["num_hidden_layers"]):
             p = f"encoder.layers.{i}."
             a = p + "attention."
-            wqkv = torch.cat([f(a + "q_proj.weight") * scale, f(a + "k_proj.weight"), f(a + "v_proj.weight")])
-            bqkv = torch.cat([f(a + "q_proj.bias") * scale, f(a + "k_proj.bias"), f(a + "v_proj.bias")])
-            P["layers"].append(dict(
-                ln1=ln(p + "layer_norm"), qkv=(m(wqkv), bqkv.contiguous()),
-                out=(m(f(a + "out_proj.weight")), f(a + "out_proj.bias")), ln2=ln(p + "final_layer_norm"),
-                w1=(m(f(p + "feed_forward.intermediate_dense.weight")), f(p + "feed_forward.intermediate_dense.bias")),
-                w2=(m(f(p + "feed_forward.output_dense.weight")), f(p + "feed_forward.output_dense.bias"))))
-        P["final_ln"] = ln("encoder.layer_norm")
+            out[f"{i}.ln1"] = ln(p + "layer_norm")
+            out[f"{i}.qkv"] = (tuple(a + n + s for s in (".weight", ".bias") for n in ("q_proj", "k_proj", "v_proj")),
+                               lambda qw, kw, vw, qb, kb, vb: (m(torch.cat([qw * scale, kw, vw])),
+                                                               torch.cat([qb * scale, kb, vb]).contiguous()))
+            out[f"{i}.out"] = lin(a + "out_proj")
+            out[f"{i}.ln2"] = ln(p + "final_layer_norm")
+            out[f"{i}.w1"] = lin(p + "feed_forward.intermediate_dense")
+            out[f"{i}.w2"] = lin(p + "feed_forward.output_dense")
+        out["final_ln"] = ln("encoder.layer_norm")
+        return out
+
+    def _prepare(self, dev, P=None):
+        """The kernel-side weights: cast, permuted and regrouped.  P: the previous ones, of which only
+        the groups whose tensors changed are rebuilt."""
+        w = self._w
+        wd = torch.bfloat16 if self.precision == "bf16" else torch.float32
+        f = lambda k: w[k].detach().to(dev, torch.float32).contiguous()
+        if P is None:
+            P = {"ver": {}, "conv": [None] * len(self.config["conv_dim"]),
+                 "layers": [{} for _ in range(self.config["num_hidden_layers"])]}
+        with torch.no_grad():
+            for name, (keys, build) in self._groups().items():
+                ver = tuple((id(w[k]), w[k]._version) for k in keys)
+                if P["ver"].get(name) == ver:
+                    continue
+                entry = build(*[f(k) for k in keys])
+                if name.startswith("conv"):
+                    P["conv"][int(name[4:])] = entry
+                elif name[0].isdigit():
+                    i, part = name.split(".")
+                    P["layers"][int(i)][part] = entry
+                else:
+                    P[name] = entry
+                P["ver"][name] = ver
         P["dev"], P["dtype"] = dev, wd
         return P
 
@@ -285,32 +369,12 @@ class Wav2Vec2(nn.Module):
         H, heads = self.config["hidden_size"], self.config["num_attention_heads"]
         return ops.w2v_attention_supported(T, heads, H // heads)
 
-    @torch.no_grad()
-    def forward(self, wav, stages=None):
-        """wav [B, N] -> [B, T_w, hidden] fp32.  stages: a dict that receives every intermediate as
-        fp32 (tests): conv0.., proj, pos, layer0.., final, out."""
-        if wav.dim() != 2:
-            raise ValueError(f"Wav2Vec2: wav must be [B, N], got {tuple(wav.shape)}")
-        if not wav.is_cuda:
-            raise TypeError("Wav2Vec2: the encoder runs on the HIP device only (there is no CPU fallback)")
-        cfg = self.config
-        B, N = wav.shape
-        T = self.n_frames(N)
-        if T < 1:
-            raise ValueError(f"Wav2Vec2: {N} samples give no frame")
-        H, heads = cfg["hidden_size"], cfg["num_attention_heads"]
-        d = H // heads
-        if not self.supported(T):
-            raise ValueError(f"Wav2Vec2: attention over T = {T} frames with {heads} heads of width {d} is "
-                             "unsupported by the HIP kernel (head width 32 or 64); there is no fallback")
-        if self._prep is None or self._prep["dev"] != wav.device or self._prep["dtype"] != (
-                torch.bfloat16 if self.precision == "bf16" else torch.float32):
-            self._prep = self._prepare(wav.device)
-        P, eps = self._prep, cfg["layer_norm_eps"]
+    def _conv_stack(self, wav, stages):
+        """normalize_wav and the seven conv layers: the last layer's fp32 output [B, T, conv_dim]."""
+        cfg, P, eps = self.config, self._prep, self.config["layer_norm_eps"]
         bf = self.precision == "bf16"
         ad = P["dtype"]
         keep = (lambda n, t: stages.__setitem__(n, t.float().clone())) if stages is not None else (lambda n, t: None)
-        act = lambda pair: pair[1] if bf else pair[0]  # w2v_rows' (fp32, bf16) -> the GEMM operand
 
         wav = wav.detach().float().contiguous()
         stats = ops.w2v_tensor_stats(wav) if self.normalize_wav else None
@@ -329,6 +393,72 @@ class Wav2Vec2(nn.Module):
             keep(f"conv{i}", x)
         if xf is None:  # a one-layer conv stack in bf16: conv0 wrote bf16
             xf = x.float()
+        return xf
+
+    def _trainable_tail(self, xf, stages):
+        """Everything from the projection upward through the autograd pieces of mlvae_hip.ops."""
+        cfg, P, w = self.config, self._prep, self._w
+        eps, bf = cfg["layer_norm_eps"], self.precision == "bf16"
+        B, T = xf.shape[0], xf.shape[1]
+        H, heads = cfg["hidden_size"], cfg["num_attention_heads"]
+        G, K = cfg["num_conv_pos_embedding_groups"], cfg["num_conv_pos_embeddings"]
+        keep = (lambda n, t: stages.__setitem__(n, t.detach().float().clone())) if stages is not None else (
+            lambda n, t: None)
+        fp = "feature_projection."
+        h = ops.W2VHeadFn.apply(xf, P, (B, T, H, G, K, eps, bf), w[fp + "layer_norm.weight"],
+                                w[fp + "layer_norm.bias"], w[fp + "projection.weight"], w[fp + "projection.bias"],
+                                w[_POS + "bias"], w[POS_G], w[POS_V])
+        keep("pos", h.view(B, T, H))
+        for i, L in enumerate(P["layers"]):
+            p = f"encoder.layers.{i}."
+            names = ["layer_norm"] + ["attention." + n for n in ("q_proj", "k_proj", "v_proj", "out_proj")] + [
+                "final_layer_norm", "feed_forward.intermediate_dense", "feed_forward.output_dense"]
+            masters = [w[p + n + s] for n in names for s in (".weight", ".bias")]
+            h = ops.W2VLayerFn.apply(h, L, (B, T, H, heads, eps, bf), *masters)
+            keep(f"layer{i}", h.view(B, T, H))
+        out = ops.W2VTailFn.apply(h, P, eps, self.output_norm, w["encoder.layer_norm.weight"],
+                                  w["encoder.layer_norm.bias"]).view(B, T, H)
+        keep("out", out)
+        return out
+
+    def forward(self, wav, stages=None):
+        """wav [B, N] -> [B, T_w, hidden] fp32.  stages: a dict that receives every intermediate as
+        fp32 (tests): conv0.., proj, pos, layer0.., final, out (fine-tuning: no proj and no final)."""
+        if self.freeze:
+            with torch.no_grad():
+                return self._forward(wav, stages)
+        return self._forward(wav, stages)
+
+    def _forward(self, wav, stages):
+        if wav.dim() != 2:
+            raise ValueError(f"Wav2Vec2: wav must be [B, N], got {tuple(wav.shape)}")
+        if not wav.is_cuda:
+            raise TypeError("Wav2Vec2: the encoder runs on the HIP device only (there is no CPU fallback)")
+        cfg = self.config
+        B, N = wav.shape
+        T = self.n_frames(N)
+        if T < 1:
+            raise ValueError(f"Wav2Vec2: {N} samples give no frame")
+        H, heads = cfg["hidden_size"], cfg["num_attention_heads"]
+        d = H // heads
+        if not self.supported(T):
+            raise ValueError(f"Wav2Vec2: attention over T = {T} frames with {heads} heads of width {d} is "
+                             "unsupported by the HIP kernel (head width 32 or 64); there is no fallback")
+        if self._prep is None or self._prep["dev"] != wav.device or self._prep["dtype"] != (
+                torch.bfloat16 if self.precision == "bf16" else torch.float32):
+            self._prep = self._prepare(wav.device)
+        elif not self.freeze:  # an optimizer step since: the changed tensors' copies only
+            self._prepare(wav.device, self._prep)
+        if not self.freeze:
+            with torch.no_grad():
+                xf = self._conv_stack(wav, stages)
+            return self._trainable_tail(xf, stages)
+        xf = self._conv_stack(wav, stages)
+        P, eps = self._prep, cfg["layer_norm_eps"]
+        bf = self.precision == "bf16"
+        ad = P["dtype"]
+        keep = (lambda n, t: stages.__setitem__(n, t.float().clone())) if stages is not None else (lambda n, t: None)
+        act = lambda pair: pair[1] if bf else pair[0]  # w2v_rows' (fp32, bf16) -> the GEMM operand
         x = act(ops.w2v_rows(xf.view(B * T, -1), gamma=P["proj_ln"][0], beta=P["proj_ln"][1], eps=eps,
                              out_f32=not bf, out_bf16=bf))
         h = ops.w2v_linear(x, *P["proj"])  # the fp32 residual stream [B T, H]
