@@ -16,6 +16,7 @@
 #ifndef MLVAE_H
 #define MLVAE_H
 #include <stddef.h>
+#include "mlvae_err.h" /* the bits of the device error words, by name */
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -232,8 +233,8 @@ int mlvae_lstm_set_debug(void* buf);
  *   boundary [B,T] 0/1 (float).  Frame t < T_i = round(T feat_len) gets target one-hot(phn[b, k])
  *   with k = (boundaries in [0, t]) - 1; loss [B,T,C] = BCE-with-logits, 0 past T_i (may be NULL);
  *   with dloss given, dlogits = dloss (sigmoid(x) - y).  The reference's asserts set *err bits:
- *   2 = boundaries do not give L_i = round(L phn_len) segments from frame 0, 4 = phoneme id
- *   outside [0, C).
+ *   MLVAE_ERR_MD_SEGMENTS = boundaries do not give L_i = round(L phn_len) segments from frame 0,
+ *   MLVAE_ERR_MD_CLASS = phoneme id outside [0, C).
  * mlvae_boundary_fwd / _bwd: BoundaryDetector after its FC heads (ref:src/modules/boundary_detector.py:
  *   42-97).  za, zb [n] = pre-Softplus head outputs, y [n] boundary targets, u [10][n] U(0,1) draws
  *   (NULL: Philox(seed) at element offset + s*n + i).  Forward: v = mean of the ten clamped
@@ -258,8 +259,8 @@ int mlvae_boundary_bwd(size_t n, const float* za, const float* zb, const float* 
  *   label = (l1 > l0), torch.argmax (a tie gives 0).
  * mlvae_pi_nll_fwd: nll [n] = logsumexp(l0, l1) - l[label] = -Categorical.log_prob(label).  labels
  *   [n] int32 are mlvae_viterbi_md's flvl_out; -1 (past T_i) counts as 0 (pad_sequence's zero
- *   fill; the length mask removes those frames).  Any other label outside {0, 1} sets bit 32 of
- *   *err (log_prob raises for it) and counts as 0.
+ *   fill; the length mask removes those frames).  Any other label outside {0, 1} sets
+ *   MLVAE_ERR_PI_LABEL in *err (log_prob raises for it) and counts as 0.
  * mlvae_pi_nll_bwd: dlogits [n,2], dlogits_k = dnll (softmax(l)_k - [k == label]). */
 int mlvae_pi_sample(size_t n, const float* logits, const float* u, unsigned long long seed,
                     unsigned long long offset, int train, float* sampled_pi, void* stream);
@@ -314,7 +315,7 @@ int mlvae_sfl_bwd(size_t n, int K, const float* logits, const float* sampled_pi,
  *     counts[b,:] int32 = over the valid frames of utterance b: both correct (pred 0, label 0),
  *       both mispronounced (1, 1), missed (0, 1), false alarm (1, 0).  The entry zeroes counts
  *       on the stream first; integer atomics, exact in any order.
- *   A valid frame whose label is neither 0 nor 1 sets bit 64 of *err (it counts as 0); labels of
+ *   A valid frame whose label is neither 0 nor 1 sets MLVAE_ERR_FLVL_LABEL in *err (it counts as 0); labels of
  *   padded frames are not looked at.
  * mlvae_flvl_head_bwd: logits [N,2] as the forward wrote them, dloss_e [N,2] the gradient of
  *   loss_e.  dlogits[i,c] = dloss_e[i,c] ((1 - y_c) sigma(x_c) - pos_w_c y_c (1 - sigma(x_c)));
@@ -337,8 +338,8 @@ int mlvae_flvl_head_bwd(int B, int T, int E, const float* h, const float* w, con
  * relative, weight = dec_weight.  Outputs (int32): boundary_out [B,T] decoded boundaries (0/1),
  * flvl_out [B,T] frame-level and plvl_out [B,L] phoneme-level mispronunciation labels (-1 past
  * T_i / L_i), lens_out [B,2] = (T_i, L_i).  ws: mlvae_viterbi_workspace_size(B,T,L) bytes (the
- * argmax path map).  *err bits: 8 = the backtrack did not end at (l, t) = (0, 0) (the reference's
- * assert), 16 = T_i or L_i empty / L_i > 1024.  L <= 1024. */
+ * argmax path map).  *err bits: MLVAE_ERR_DECODE_BACKTRACK = the backtrack did not end at (l, t) =
+ * (0, 0) (the reference's assert), MLVAE_ERR_DECODE_EMPTY = T_i or L_i empty / L_i > 1024.  L <= 1024. */
 size_t mlvae_viterbi_workspace_size(int B, int T, int L);
 int mlvae_viterbi_md(int B, int T, int N, int L, const float* logits, int ldl, const float* boundary_v,
                      const float* pi_logits, const float* prior, const long long* seqs,
@@ -376,7 +377,7 @@ int mlvae_viterbi_md_ex(int B, int T, int N, int L, const float* logits, int ldl
  *   redraws nothing (it reads ysoft) and takes no map.
  * mlvae_viterbi_md_ex (declared above): skip_empty != 0 makes a row with T_i == 0 and L_i == 0 --
  *   the zero-length filler of a short rank slice -- write -1 everywhere and lens_out (0, 0)
- *   without an error bit; every other empty or oversized row still sets bit 16.  skip_empty == 0
+ *   without an error bit; every other empty or oversized row still sets MLVAE_ERR_DECODE_EMPTY.  skip_empty == 0
  *   is mlvae_viterbi_md. */
 int mlvae_randn_rows(int B, int T, int C, unsigned long long seed, const long long* map, float* out,
                      void* stream);
@@ -842,7 +843,7 @@ int mlvae_hvae_latent_bwd(int rows, int N, int Z, const float* ml, int ldml, con
  *   classes equals flvl_tgt[b,t] (torch.argmax: the first maximal index, a NaN is the maximum; a
  *   target outside [0, C) never matches).  plvl_correct: the flags == 1 in [0, T_b) open the
  *   segments, segment k runs to the next flag or T_b; its class sums are fp32 from 0 over the
- *   frames in increasing t; their argmax is compared with plvl_tgt[b,k].  Bit 128 of *err (the
+ *   frames in increasing t; their argmax is compared with plvl_tgt[b,k].  MLVAE_ERR_SCORE_SEGMENTS in *err (the
  *   reference's two asserts): the flags are not L_b many, or the first is not at frame 0 with
  *   T_b > 0; that utterance's plvl_correct is 0.  A row with T_b == 0 and L_b == 0 (the filler of
  *   a short data-parallel slice) gives zeros and no error.  plvl_tgt == NULL: (.., .., 0, 0).
@@ -851,7 +852,7 @@ int mlvae_hvae_latent_bwd(int rows, int N, int Z, const float* ml, int ldml, con
  *   other valid frames, -1 past T_b.  Order: value descending, then index ascending; a NaN ranks
  *   above every number (torch.topk); frame i is chosen iff fewer than k_b frames precede it.  The
  *   row is ranked in LDS: T > mlvae_boundary_topk_max_frames() (12288) gives status 1.  k_b > T_b
- *   sets bit 256 of *err (torch.topk raises) and the row gets no ones.
+ *   sets MLVAE_ERR_SCORE_K in *err (torch.topk raises) and the row gets no ones.
  * mlvae_boundary_score: pred [B,T] int32 (mlvae_boundary_topk's, or the decode's boundary_out),
  *   target [B,T] floats.  counts[b] = (correct, n_pred, n_target) over t < T_b: the frames with
  *   pred == 1 walked in time order against the true segments [start_s, start_{s+1}] (both ends
@@ -877,9 +878,9 @@ int mlvae_boundary_score(int B, int T, const int* pred, const float* target, con
  * classes, start in node 0 or 1, end in one of the last two.  A path scores the sum of its
  * emissions.  A chain may have mlvae_lattice_max_nodes() (1024) nodes, counted on the padded L:
  * beyond it, status 1.
- * *err bits (device word, OR-ed): 512 = HMM chain infeasible (T_b < U_b, U_b = 0 or T_b = 0);
- *   1024 = a phoneme id whose state class is outside [0, C); 2048 = CTC, a target class equal to
- *   blank.  Such an utterance scores 0 with gradient 0 and alignment -1.  A CTC chain without a
+ * *err bits (device word, OR-ed): MLVAE_ERR_ALIGN_SHORT = HMM chain infeasible (T_b < U_b, U_b = 0
+ *   or T_b = 0); MLVAE_ERR_ALIGN_CLASS = a phoneme id whose state class is outside [0, C);
+ *   MLVAE_ERR_ALIGN_BLANK = CTC, a target class equal to blank.  Such an utterance scores 0 with gradient 0 and alignment -1.  A CTC chain without a
  *   path is no error: score 0, gradient 0 (torch's zero_infinity).
  * mlvae_lattice_fb: score[b] = log sum over the paths of exp(path score); alpha (and, with
  *   need_beta, beta: the chain run backwards, concurrently) go to the workspace (fp32, renormalised
@@ -941,7 +942,7 @@ int mlvae_center_lsm_bwd(int B, int T, int C, const float* dy, const float* y, f
  * mlvae_ctc_md_counts: counts [B,8] int32 over the alignment to the pronounced sequence, with
  *   pred_md = (ali != canonical) (a deletion counts as mispronounced) and gt_md = (pronounced !=
  *   canonical): (both correct, both mispronounced, missed, false alarm, canonical positions, of
- *   them recognised wrongly, mispronounced positions, of them recognised wrongly).  *err bit 4096:
+ *   them recognised wrongly, mispronounced positions, of them recognised wrongly).  *err bit MLVAE_ERR_CTC_PAIR:
  *   the two references of an utterance differ in length (the shorter is counted).
  * mlvae_ctc_viterbi: the best path of the CTC chain over phns [B,L] (blank, p_0, blank, .., blank;
  *   stay / next / skip over a blank between two different classes; start in node 0 or 1, end in one
@@ -949,7 +950,7 @@ int mlvae_center_lsm_bwd(int B, int T, int C, const float* dy, const float* y, f
  *   tie keeps the final blank.  vscore [B] = the path's score rounded once; boundary [B,T] int32 = 1
  *   at frame 0 and at the first frame of phoneme k = 1 .. L_b - 1 (exactly L_b ones), 0 at the other
  *   frames t < T_b, -1 past T_b.  A chain without a path (T_b too short, or T_b = 0) is no error:
- *   vscore 0, infeasible[b] = 1, ones at frames 0 .. min(L_b, T_b) - 1.  *err bits 1024 / 2048 as the
+ *   vscore 0, infeasible[b] = 1, ones at frames 0 .. min(L_b, T_b) - 1.  *err bits MLVAE_ERR_ALIGN_CLASS / _BLANK as the
  *   lattice's (then vscore 0, boundary -1, infeasible 0).  2 L + 1 above 1024 nodes: status 1.  ws:
  *   mlvae_ctc_viterbi_workspace_size(B, T) bytes (two backpointer bits per node and frame).
  * mlvae_log_softmax_fwd / _bwd: y = log_softmax(x) over the C columns of `rows` contiguous rows, and
@@ -1033,8 +1034,9 @@ int mlvae_fbank(int B, int Nmax, const float* wav, int ld, const int* n_samples,
  * utterances in row order and their frames in time order (a fixed order, no floating-point
  * atomics: a rerun is bit-identical).  mlvae_cmvn_apply, in place on rows t < frames[b]:
  * mean = sum x / n, var = max(sum x^2 / n - mean^2, 1e-20), y = (x - mean) / sqrt(var); rows past
- * frames[b] are not touched.  err: a device int32 word the kernels OR into: bit 0 a speaker id
- * outside [0, S) (that utterance is skipped), bit 1 (apply) a speaker with n = 0 (left as it is).
+ * frames[b] are not touched.  err: a device int32 word of its own the kernels OR into: MLVAE_CMVN_ERR_SPEAKER
+ * a speaker id outside [0, S) (that utterance is skipped), MLVAE_CMVN_ERR_NO_STATS (apply) a speaker with
+ * n = 0 (left as it is).
  * Limits (status 1): D <= 1024, S >= 1, B <= 65535. */
 size_t mlvae_kaldi_fbank_table_size(int L, int P, int n_mels);
 size_t mlvae_kaldi_fbank_workspace_size(int B, int Nmax, int hop, int n_mels);

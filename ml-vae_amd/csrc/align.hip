@@ -40,15 +40,7 @@ constexpr int AL_MAX_NODES = 1024;  // nodes of one chain: 64 lanes x at most 16
 constexpr int AL_PF = 4;            // frames of gathered emissions in flight
 constexpr int AL_RN = 4;            // frames between two renormalisations
 constexpr int AL_TOPO_HMM = 0, AL_TOPO_CTC = 1;
-constexpr int ALIGN_ERR_SHORT = 512;    // bit of *err: HMM chain infeasible (T_b < U_b, U_b = 0 or T_b = 0)
-constexpr int ALIGN_ERR_CLASS = 1024;   // bit of *err: a phoneme id whose state class is outside [0, C)
-constexpr int ALIGN_ERR_BLANK = 2048;   // bit of *err: CTC, a target class equal to blank
 constexpr float NINF = -INFINITY;
-
-__device__ __forceinline__ int round_len(float rel, int n) {
-  int r = (int)rintf((float)n * rel);
-  return r < 0 ? 0 : (r > n ? n : r);
-}
 
 // One utterance's chain: lengths and the class of a node.
 struct Chain {
@@ -80,10 +72,10 @@ struct Chain {
 };
 
 // The data errors of one chain, decided by a whole wave the same way in every kernel that walks
-// it (nodes strided over the lanes): bits of ALIGN_ERR_*.
+// it (nodes strided over the lanes): bits of MLVAE_ERR_ALIGN_*.
 __device__ __forceinline__ int chain_errors(const Chain& ch, int lane) {
   int bits = 0;
-  if (!ch.shape_ok()) return ch.topo == AL_TOPO_HMM ? ALIGN_ERR_SHORT : 0;
+  if (!ch.shape_ok()) return ch.topo == AL_TOPO_HMM ? MLVAE_ERR_ALIGN_SHORT : 0;
   bool bad = false, blk = false;
   for (int n = lane; n < ch.N; n += 64) {
     if (!ch.is_target(n)) continue;
@@ -91,15 +83,9 @@ __device__ __forceinline__ int chain_errors(const Chain& ch, int lane) {
     bad |= c < 0;
     blk |= ch.topo == AL_TOPO_CTC && c == ch.blank;
   }
-  if (__any(bad)) bits |= ALIGN_ERR_CLASS;
-  if (__any(blk)) bits |= ALIGN_ERR_BLANK;
+  if (__any(bad)) bits |= MLVAE_ERR_ALIGN_CLASS;
+  if (__any(blk)) bits |= MLVAE_ERR_ALIGN_BLANK;
   return bits;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
 }
 
 // log(exp a + exp b [+ exp c]) on the hardware exp / log: the step is on the serial path; the

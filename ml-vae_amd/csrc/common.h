@@ -4,6 +4,7 @@
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "../../include/mlvae_err.h"  // the device error words' bits
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -13,6 +14,7 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));  // fp8 MFMA operand (32 e4m3 per lane)
 typedef int i32x4 __attribute__((ext_vector_type(4)));  // raw buffer-resource words (asm operands)
+typedef __attribute__((address_space(3))) bf16x4* lds_b4_p;  // ds_read_b64_tr_b16's LDS operand
 
 // Compute precision of a matrix product (operands; accumulation is always fp32).
 enum MlvaePrec { PREC_F32 = 0, PREC_BF16 = 1 };
@@ -114,6 +116,15 @@ __device__ __forceinline__ int valid_frames(float rel_len, int T) {
   return c >= (float)T ? T : (int)c;
 }
 
+// Absolute length of a relative one over n padded positions (SpeechBrain's round(rel * n)),
+// clamped to [0, n]: the frames / phonemes the scoring, lattice and CTC evaluation kernels count.
+__device__ __forceinline__ int round_len(float rel, int n) {
+  int r = (int)rintf((float)n * rel);
+  return r < 0 ? 0 : (r > n ? n : r);
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
 // Total valid frames for a workgroup: *count when given (data parallel: the all-reduced global
 // count), else summed by the whole workgroup -- integers, so exact in any order.  Every thread
 // must call it (two barriers); all get the result.  (A single thread walking B lengths serially
@@ -148,6 +159,25 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// ---- the bf16 MFMA (16 x 16 x 32, fp32 accumulate) and its transposed LDS operand read
+__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+// operand fragment (m or n = base + (lane & 15), k = kk + 8 (lane >> 4) + e) of an LDS image
+// stored [k rows][ld], read transposed (the MC fragment of gemm_fast.hip, unswizzled)
+__device__ __forceinline__ bf16x8 trfrag(const short* img, int ld, int base, int kk, int lane) {
+  const int g = lane >> 4, i4 = lane & 15, qq = i4 >> 2, pp = i4 & 3;
+  const int r1 = kk + 8 * g + qq, r2 = r1 + 4;
+  const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_b4_p)(img + r1 * ld + base + 4 * pp));
+  const bf16x4 v2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_b4_p)(img + r2 * ld + base + 4 * pp));
+  return bf16x8{v1[0], v1[1], v1[2], v1[3], v2[0], v2[1], v2[2], v2[3]};
+}
 
 // Counter-based Philox-4x32-10 (four 32-bit words per counter), keyed by a 64-bit seed.
 __device__ __forceinline__ void philox4(unsigned long long seed, unsigned long long ctr,
@@ -163,6 +193,14 @@ __device__ __forceinline__ void philox4(unsigned long long seed, unsigned long l
     k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
   }
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// Exp(1) sample as torch's exponential_: -log(u), u in (0, 1) (strictly positive, finite)
+__device__ __forceinline__ float exp1(unsigned long long seed, unsigned long long i) {
+  unsigned r[4];
+  philox4(seed, i, r);
+  const float u = ((float)(r[0] >> 8) + 0.5f) * (1.f / 16777216.f);
+  return -logf(u);
 }
 
 // ---- the utterance map of a data-parallel shard ("The utterance map").

@@ -30,22 +30,6 @@ constexpr int BM = 64;     // frames per tile (4 waves x 16)
 constexpr int CT = 256;    // threads
 constexpr int SKEW = 8;    // shorts of row padding in the LDS images
 constexpr int MTW = 8;     // weight-gradient m-tiles per wave (K * Cin16 <= 512)
-typedef __attribute__((address_space(3))) bf16x4* lds_b4_p;
-
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-// operand fragment (m = base + (lane & 15), k = kk + 8 (lane >> 4) + e) of an LDS image stored
-// [k rows][ld] (k = frames), read transposed
-__device__ __forceinline__ bf16x8 trfrag(const short* img, int ld, int base, int kk, int lane) {
-  const int g = lane >> 4, i4 = lane & 15, qq = i4 >> 2, pp = i4 & 3;
-  const int r1 = kk + 8 * g + qq, r2 = r1 + 4;
-  const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_b4_p)(img + r1 * ld + base + 4 * pp));
-  const bf16x4 v2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_b4_p)(img + r2 * ld + base + 4 * pp));
-  return bf16x8{v1[0], v1[1], v1[2], v1[3], v2[0], v2[1], v2[2], v2[3]};
-}
-
 // Rows [t_first, t_first + R) of utterance b (zero outside [0, T) and for channels >= C) of an
 // fp32 source [N][lds], element group e = tid + j * CT (row e / (CP / 4), channels 4 (e % (CP / 4))
 // ...): NL 16-byte loads per thread, all issued before any is used, so a tile's rows are in

@@ -39,22 +39,6 @@ namespace {
 
 constexpr int CT = 256;
 constexpr int LDT = 72;  // shorts per row of the weight gradient's LDS images (64 + 8 skew)
-typedef __attribute__((address_space(3))) bf16x4* lds_b4_p;
-
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-// operand fragment (m = base + (lane & 15), k = kk + 8 (lane >> 4) + e) of an LDS image stored
-// [k rows][ld], read transposed (as conv.hip's weight gradient)
-__device__ __forceinline__ bf16x8 trfrag(const short* img, int ld, int base, int kk, int lane) {
-  const int g = lane >> 4, i4 = lane & 15, qq = i4 >> 2, pp = i4 & 3;
-  const int r1 = kk + 8 * g + qq, r2 = r1 + 4;
-  const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_b4_p)(img + r1 * ld + base + 4 * pp));
-  const bf16x4 v2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_b4_p)(img + r2 * ld + base + 4 * pp));
-  return bf16x8{v1[0], v1[1], v1[2], v1[3], v2[0], v2[1], v2[2], v2[3]};
-}
-
 // deterministic workgroup sum (4 waves): butterfly per wave, the waves in order
 __device__ __forceinline__ float block_sum(float v, float* sh) {
   v = wave_sum(v);

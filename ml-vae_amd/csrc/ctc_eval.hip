@@ -36,21 +36,7 @@ namespace {
 constexpr int CE_MAX_REF = 1024;    // reference tokens of one alignment: 64 lanes x at most 16 rows
 constexpr int CE_MAX_NODES = 1024;  // nodes of one CTC chain, as align.hip's
 constexpr int CE_PF = 4;            // frames of gathered emissions in flight
-constexpr int CE_ERR_CLASS = 1024;  // bit of *err (align.hip's): a phoneme id outside [0, C)
-constexpr int CE_ERR_BLANK = 2048;  // bit of *err (align.hip's): a target class equal to blank
-constexpr int CE_ERR_PAIR = 4096;   // bit of *err: pronounced and canonical sequences differ in length
 constexpr float NINF = -INFINITY;
-
-__device__ __forceinline__ int round_len(float rel, int n) {
-  int r = (int)rintf((float)n * rel);
-  return r < 0 ? 0 : (r > n ? n : r);
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 __device__ __forceinline__ int wave_sum_i(int v) {
 #pragma unroll
@@ -254,7 +240,7 @@ __global__ __launch_bounds__(64) void ctc_md_counts_kernel(int L, const long lon
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) counts[(size_t)b * 8 + k] = c[k];
-    if (Lp != Lc) atomicOr(err, CE_ERR_PAIR);
+    if (Lp != Lc) atomicOr(err, MLVAE_ERR_CTC_PAIR);
   }
 }
 
@@ -281,7 +267,7 @@ __global__ __launch_bounds__(64) void ctc_viterbi_kernel(
     bad |= p < 0 || p >= C;
     blk |= p == blank;
   }
-  const int bits = (__any(bad) ? CE_ERR_CLASS : 0) | (__any(blk) ? CE_ERR_BLANK : 0);
+  const int bits = (__any(bad) ? MLVAE_ERR_ALIGN_CLASS : 0) | (__any(blk) ? MLVAE_ERR_ALIGN_BLANK : 0);
   if (bits || Tb == 0) {  // a bad id is an error; no frames is a chain without a path
     for (int t = lane; t < T; t += 64) brow[t] = -1;
     if (lane == 0) {

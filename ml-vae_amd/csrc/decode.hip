@@ -69,7 +69,7 @@ __global__ __launch_bounds__(DT) void viterbi_kernel(DecArgs a) {
   // utterances: -1 everywhere and lens (0, 0) as written above, and nothing to report
   if (a.skip_empty && Ti == 0 && Li == 0) return;
   if (Ti <= 0 || Li <= 0 || Li > MAXL) {
-    if (tid == 0) atomicOr(a.err, 16);
+    if (tid == 0) atomicOr(a.err, MLVAE_ERR_DECODE_EMPTY);
     return;  // the whole workgroup leaves before any barrier
   }
   const float w32 = a.weight;
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(DT) void viterbi_kernel(DecArgs a) {
   }
   if (tid == 0) {
     a.bnd_out[(size_t)b * T] = 1;  // boundary at frame 0 (appended after the loop)
-    if (bl != 0 || nph != Li) atomicOr(a.err, 8);  // assert l == t == 0 (decode_utils.py:529)
+    if (bl != 0 || nph != Li) atomicOr(a.err, MLVAE_ERR_DECODE_BACKTRACK);  // assert l == t == 0 (decode_utils.py:529)
   }
   __syncthreads();
   for (int t = tid; t < Ti; t += DT)

@@ -28,12 +28,6 @@ namespace {
 
 constexpr int EW = 64;   // encoder width E
 constexpr int ZW = 32;   // latent width z
-typedef __attribute__((address_space(3))) bf16x4* lds_b4_p;
-
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
 __device__ __forceinline__ int perm_k(int kk, int q, int e) {
   return 32 * kk + (e < 4 ? 4 * q + e : 12 + 4 * q + e);
 }
@@ -90,16 +84,6 @@ __device__ __forceinline__ bf16x8 next_frag_lo(float (*h)[4], int kk) {
   return bf16x8{f2bf_lo(h[2 * kk][0]), f2bf_lo(h[2 * kk][1]), f2bf_lo(h[2 * kk][2]), f2bf_lo(h[2 * kk][3]),
                 f2bf_lo(h[2 * kk + 1][0]), f2bf_lo(h[2 * kk + 1][1]), f2bf_lo(h[2 * kk + 1][2]),
                 f2bf_lo(h[2 * kk + 1][3])};
-}
-
-// operand fragment (m or n = base + (lane & 15), k = kk + 8 (lane >> 4) + e) of an LDS image
-// stored [k rows][ld], read transposed (the MC fragment of gemm_fast.hip, unswizzled)
-__device__ __forceinline__ bf16x8 trfrag(const short* img, int ld, int base, int kk, int lane) {
-  const int g = lane >> 4, i4 = lane & 15, qq = i4 >> 2, pp = i4 & 3;
-  const int r1 = kk + 8 * g + qq, r2 = r1 + 4;
-  const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_b4_p)(img + r1 * ld + base + 4 * pp));
-  const bf16x4 v2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_b4_p)(img + r2 * ld + base + 4 * pp));
-  return bf16x8{v1[0], v1[1], v1[2], v1[3], v2[0], v2[1], v2[2], v2[3]};
 }
 
 // standard normal of counter i: the same draw as mlvae_randn (elbo.hip randn_kernel)

@@ -85,8 +85,6 @@ bool geo_ok(const char* who, int hop, int win, int n_fft, int n_mels) {
 size_t table_floats(const Geo& g) { return (size_t)g.wr * g.ldt + (size_t)g.K * MELP; }
 size_t lds_bytes(const Geo& g) { return ((size_t)FT * g.lda + (size_t)FT * g.ldp) * sizeof(float); }
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 __global__ __launch_bounds__(NT) void fbank_tile_kernel(
     Geo g, int Nmax, int Tmax, int ntiles, const float* __restrict__ wav, int ld,
     const int* __restrict__ n_samples, const float* __restrict__ table, float* __restrict__ ws_db,

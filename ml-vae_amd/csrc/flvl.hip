@@ -22,7 +22,6 @@ constexpr int FL_FRAMES = 256 / FL_LANES;  // frames per block (forward)
 constexpr int FL_CHUNK = 256;              // frames per backward chunk: one per thread
 constexpr int FL_FWD_GRID = 4096;          // grid caps: 65536 frames a sweep, either way
 constexpr int FL_BWD_GRID = 256;
-constexpr int FLVL_ERR_LABEL = 64;         // bit of *err: a valid frame's label is neither 0 nor 1
 
 // softplus(x) = log(1 + e^x), finite at any x
 __device__ __forceinline__ float softplus_(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
@@ -71,7 +70,7 @@ __global__ __launch_bounds__(256) void flvl_fwd_kernel(
       int p = -1;
       if (t < valid_frames(lens[b], T)) {
         p = x1 > x0 ? 1 : 0;  // torch.argmax: the first maximum on a tie
-        if (l != 0.f && l != 1.f) bad = FLVL_ERR_LABEL;
+        if (l != 0.f && l != 1.f) bad = MLVAE_ERR_FLVL_LABEL;
         const int g = l == 1.f ? 1 : 0;
         // md_metric_stats._counts: both correct, both mispronounced, missed, false alarm
         atomicAdd(counts + 4 * b + (p == g ? g : (g ? 2 : 3)), 1);

@@ -37,14 +37,6 @@ struct GmmArgs {
 
 constexpr int GMM_MAX_N = 64;
 
-// Exp(1) sample as torch's exponential_: -log(u), u in (0, 1) (strictly positive, finite)
-__device__ __forceinline__ float exp1(unsigned long long seed, unsigned long long i) {
-  unsigned r[4];
-  philox4(seed, i, r);
-  const float u = ((float)(r[0] >> 8) + 0.5f) * (1.f / 16777216.f);
-  return -logf(u);
-}
-
 // MAP: the Exp(1) draw of (row r, component n) is stream element (g T + t) N + n (common.h
 // UttMap), what the single process draws for that frame
 template <bool MAP>

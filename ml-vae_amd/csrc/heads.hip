@@ -66,17 +66,8 @@ __device__ __forceinline__ void rows16_to_lds(f32x4 v, float* dst, int lane) {
 }
 
 __device__ __forceinline__ bf16x8 lds8(const short* p) { return *reinterpret_cast<const bf16x8*>(p); }
-typedef __attribute__((address_space(3))) bf16x4* lds_b4h_p;
-// MFMA operand fragment (m or n = base + (lane & 15), k = kk + 8 (lane >> 4) + e) of an LDS image
-// stored [k rows][ld], read transposed by ds_read_b64_tr_b16: the weight gradients below take
-// the frame rows as K
-__device__ __forceinline__ bf16x8 trk(const short* img, int ld, int base, int kk, int lane) {
-  const int g = lane >> 4, i4 = lane & 15, qq = i4 >> 2, pp = i4 & 3;
-  const int r1 = kk + 8 * g + qq, r2 = r1 + 4;
-  const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_b4h_p)(img + r1 * ld + base + 4 * pp));
-  const bf16x4 v2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_b4h_p)(img + r2 * ld + base + 4 * pp));
-  return bf16x8{v1[0], v1[1], v1[2], v1[3], v2[0], v2[1], v2[2], v2[3]};
-}
+// the weight gradients below take the frame rows as K: their operands are common.h's trfrag (an
+// LDS image stored [k rows][ld], read transposed by ds_read_b64_tr_b16)
 // weight-gradient tiles (16 x 16) of the fused form: dW3 of both heads [F x C], then dW2 [C x C]
 template <int C, int F> constexpr int nt3() { return 2 * (F / 16) * (C / 16); }
 template <int C, int F> constexpr int nt2() { return 2 * (C / 16) * (C / 16); }
@@ -93,9 +84,6 @@ __device__ __forceinline__ void st_saved(float* base, size_t idx, f32x4 v, int s
 }
 __device__ __forceinline__ bf16x8 gld8(const unsigned short* p) {
   return *reinterpret_cast<const bf16x8*>(p);
-}
-__device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
 template <int C, int F>
@@ -188,7 +176,7 @@ __global__ __launch_bounds__(256) void heads_kernel(HeadArgs a) {
       for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int j = 0; j < NC2; ++j)
-          acc1[j] = mfma(lds8(Wb + (16 * j + l15) * LS1 + 32 * s + 8 * q), ac[s], acc1[j]);
+          acc1[j] = mfma16(lds8(Wb + (16 * j + l15) * LS1 + 32 * s + 8 * q), ac[s], acc1[j]);
       if (kc + 1 < nk) wstore((kc + 1) & 1);
       __syncthreads();
       ac[0] = an[0]; ac[1] = an[1];
@@ -215,7 +203,7 @@ __global__ __launch_bounds__(256) void heads_kernel(HeadArgs a) {
       const bf16x8 av = lds8(sm + O_P1 + lrow * L2C + h * C + kk + 8 * q);
 #pragma unroll
       for (int j = 0; j < NC; ++j)
-        acc2[h][j] = mfma(lds8(sm + O_W2I + h * C * LC + (16 * j + l15) * LC + kk + 8 * q), av, acc2[h][j]);
+        acc2[h][j] = mfma16(lds8(sm + O_W2I + h * C * LC + (16 * j + l15) * LC + kk + 8 * q), av, acc2[h][j]);
     }
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
@@ -232,7 +220,7 @@ __global__ __launch_bounds__(256) void heads_kernel(HeadArgs a) {
       const bf16x8 av = lds8(sm + O_P2 + h * RT * LC + lrow * LC + kk + 8 * q);
 #pragma unroll
       for (int j = 0; j < NF; ++j)
-        acc3[h][j] = mfma(lds8(sm + O_W3I + h * F * LC + (16 * j + l15) * LC + kk + 8 * q), av, acc3[h][j]);
+        acc3[h][j] = mfma16(lds8(sm + O_W3I + h * F * LC + (16 * j + l15) * LC + kk + 8 * q), av, acc3[h][j]);
     }
 #pragma unroll
     for (int j = 0; j < NF; ++j) {
@@ -322,7 +310,7 @@ __global__ __launch_bounds__(256) void heads_kernel(HeadArgs a) {
         const bf16x8 av = lds8(sm + O_DO + h * RT * LF + lrow * LF + kk + 8 * q);
 #pragma unroll
         for (int j = 0; j < NC; ++j)
-          acc5[j] = mfma(lds8(sm + O_W3T + h * C * LF + (16 * j + l15) * LF + kk + 8 * q), av, acc5[j]);
+          acc5[j] = mfma16(lds8(sm + O_W3T + h * C * LF + (16 * j + l15) * LF + kk + 8 * q), av, acc5[j]);
       }
     }
 #pragma unroll
@@ -344,7 +332,7 @@ __global__ __launch_bounds__(256) void heads_kernel(HeadArgs a) {
         const bf16x8 av = lds8(sm + O_P2 + h * RT * LC + lrow * LC + kk + 8 * q);
 #pragma unroll
         for (int j = 0; j < NC; ++j)
-          acc6[j] = mfma(lds8(sm + O_W2T + h * C * LC + (16 * j + l15) * LC + kk + 8 * q), av, acc6[j]);
+          acc6[j] = mfma16(lds8(sm + O_W2T + h * C * LC + (16 * j + l15) * LC + kk + 8 * q), av, acc6[j]);
       }
     }
 #pragma unroll
@@ -382,7 +370,7 @@ __global__ __launch_bounds__(256) void heads_kernel(HeadArgs a) {
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int s7 = 0; s7 < C2 / 32; ++s7)
-        acc = mfma(lds8(sm + O_S7 + (16 * j + l15) * L2C + 32 * s7 + 8 * q), af[s7], acc);
+        acc = mfma16(lds8(sm + O_S7 + (16 * j + l15) * L2C + 32 * s7 + 8 * q), af[s7], acc);
       if (rv) *reinterpret_cast<f32x4*>(dyrow + n0 + 16 * j + 4 * q) = acc;
     }
   }
@@ -549,9 +537,9 @@ __global__ __launch_bounds__(256) void heads_mid_kernel(HeadArgs a) {
         const bf16x8 av = lds8(sm + O_P1 + lrow * L2C + h * C + kk + 8 * q);
 #pragma unroll
         for (int j = 0; j < NC; ++j) {
-          acc2[h][j] = mfma(lds8(sm + O_W2I + h * C * LC + (16 * j + l15) * LC + kk + 8 * q), av, acc2[h][j]);
+          acc2[h][j] = mfma16(lds8(sm + O_W2I + h * C * LC + (16 * j + l15) * LC + kk + 8 * q), av, acc2[h][j]);
           if constexpr (SPL)
-            acc2[h][j] = mfma(lds8(sm + O_W2T + h * C * LC + (16 * j + l15) * LC + kk + 8 * q), av, acc2[h][j]);
+            acc2[h][j] = mfma16(lds8(sm + O_W2T + h * C * LC + (16 * j + l15) * LC + kk + 8 * q), av, acc2[h][j]);
         }
       }
 #pragma unroll
@@ -571,9 +559,9 @@ __global__ __launch_bounds__(256) void heads_mid_kernel(HeadArgs a) {
 #pragma unroll
         for (int j = 0; j < NF; ++j) {
           const short* wr = sm + O_W3I + h * W3R * LC + (16 * j + l15) * LC;
-          acc3[h][j] = mfma(lds8(wr + kk + 8 * q), av, acc3[h][j]);
+          acc3[h][j] = mfma16(lds8(wr + kk + 8 * q), av, acc3[h][j]);
           if constexpr (SPL) {
-            acc3[h][j] = mfma(lds8(sm + O_W3T + h * F * LC + (16 * j + l15) * LC + kk + 8 * q), av, acc3[h][j]);
+            acc3[h][j] = mfma16(lds8(sm + O_W3T + h * F * LC + (16 * j + l15) * LC + kk + 8 * q), av, acc3[h][j]);
             // P2_lo W3_hi^T: the lo fragment of k-step kk / 32 straight from the stage-2 results
             // (tiles 2s, 2s + 1: k = kk + 4 q + r and kk + 16 + 4 q + r), W3_hi read in that order
             const int s2 = kk / 32;
@@ -583,7 +571,7 @@ __global__ __launch_bounds__(256) void heads_mid_kernel(HeadArgs a) {
                                f2bf_lo(acc2[h][2 * s2 + 1][2]), f2bf_lo(acc2[h][2 * s2 + 1][3])};
             const bf16x4 w0 = *reinterpret_cast<const bf16x4*>(wr + kk + 4 * q);
             const bf16x4 w1 = *reinterpret_cast<const bf16x4*>(wr + kk + 16 + 4 * q);
-            acc3[h][j] = mfma(bf16x8{w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]}, pl, acc3[h][j]);
+            acc3[h][j] = mfma16(bf16x8{w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]}, pl, acc3[h][j]);
           }
         }
       }
@@ -645,8 +633,8 @@ __global__ __launch_bounds__(256) void heads_mid_kernel(HeadArgs a) {
         if (h < nh) {
 #pragma unroll
           for (int kk = 0; kk < RT; kk += 32)
-            aw3[i] = mfma(trk(sm + O_DO + h * RT * LF, LF, 16 * fb, kk, lane),
-                          trk(sm + O_P2 + h * RT * LC, LC, 16 * cb, kk, lane), aw3[i]);
+            aw3[i] = mfma16(trfrag(sm + O_DO + h * RT * LF, LF, 16 * fb, kk, lane),
+                          trfrag(sm + O_P2 + h * RT * LC, LC, 16 * cb, kk, lane), aw3[i]);
         }
       }
       lds_barrier();
@@ -664,7 +652,7 @@ __global__ __launch_bounds__(256) void heads_mid_kernel(HeadArgs a) {
           const bf16x8 av = lds8(sm + O_DO + h * RT * LF + lrow * LF + kk + 8 * q);
 #pragma unroll
           for (int j = 0; j < NC; ++j)
-            acc5[j] = mfma(SPL ? trk(sm + O_W3I + h * W3R * LC, LC, 16 * j, kk, lane)
+            acc5[j] = mfma16(SPL ? trfrag(sm + O_W3I + h * W3R * LC, LC, 16 * j, kk, lane)
                                : lds8(sm + O_W3T + h * C * LF + (16 * j + l15) * LF + kk + 8 * q), av, acc5[j]);
         }
       }
@@ -686,7 +674,7 @@ __global__ __launch_bounds__(256) void heads_mid_kernel(HeadArgs a) {
           const bf16x8 av = lds8(sm + O_P2 + h * RT * LC + lrow * LC + kk + 8 * q);
 #pragma unroll
           for (int j = 0; j < NC; ++j)
-            acc6[j] = mfma(SPL ? trk(sm + O_W2I + h * C * LC, LC, 16 * j, kk, lane)
+            acc6[j] = mfma16(SPL ? trfrag(sm + O_W2I + h * C * LC, LC, 16 * j, kk, lane)
                                : lds8(sm + O_W2T + h * C * LC + (16 * j + l15) * LC + kk + 8 * q), av, acc6[j]);
         }
       }
@@ -714,8 +702,8 @@ __global__ __launch_bounds__(256) void heads_mid_kernel(HeadArgs a) {
         if (h < nh) {
 #pragma unroll
           for (int kk = 0; kk < RT; kk += 32)
-            aw2[i] = mfma(trk(sm + O_P2 + h * RT * LC, LC, 16 * ob, kk, lane),
-                          trk(sm + O_P1, L2C, h * C + 16 * ib, kk, lane), aw2[i]);
+            aw2[i] = mfma16(trfrag(sm + O_P2 + h * RT * LC, LC, 16 * ob, kk, lane),
+                          trfrag(sm + O_P1, L2C, h * C + 16 * ib, kk, lane), aw2[i]);
         }
       }
     }
@@ -873,7 +861,7 @@ __global__ __launch_bounds__(512) void heads_nt_kernel(int M, int Nn, int K, con
 #pragma unroll
         for (int nt = 0; nt < HNT_BN / 16; ++nt) {
           const int brow = 32 * (nt >> 1) + 8 * (l15 >> 2) + 4 * (nt & 1) + (l15 & 3);
-          acc[nt] = mfma(*reinterpret_cast<const bf16x8*>(bb + brow * HNT_LB + 32 * ks + 8 * q),
+          acc[nt] = mfma16(*reinterpret_cast<const bf16x8*>(bb + brow * HNT_LB + 32 * ks + 8 * q),
                          afr[ks % (AKC / 32)], acc[nt]);
         }
       buf ^= 1;

@@ -50,14 +50,6 @@ struct HvaeArgs {
   UttMap m; unsigned T;  // MAP: rows = B T frames of a shard (common.h UttMap)
 };
 
-// Exp(1) sample as torch's exponential_ (gmm.hip exp1)
-__device__ __forceinline__ float exp1(unsigned long long seed, unsigned long long i) {
-  unsigned r[4];
-  philox4(seed, i, r);
-  const float u = ((float)(r[0] >> 8) + 0.5f) * (1.f / 16777216.f);
-  return -logf(u);
-}
-
 // (logit + Gumbel) / tau of component n of row r (gr = the row's index in the draw stream)
 __device__ __forceinline__ float gumbel_u(const HvaeArgs& a, const float* lg, size_t r,
                                           unsigned long long gr, int n) {

@@ -92,8 +92,6 @@ size_t table_floats(const Geo& g) { return (size_t)g.wr * g.ldt + (size_t)g.K * 
 size_t lds_bytes(const Geo& g) { return ((size_t)FT * g.lda + (size_t)FT * g.ldp) * sizeof(float); }
 long long frames_of(long long N, int shift) { return (N + shift / 2) / shift; }
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 __global__ __launch_bounds__(NT) void kaldi_tile_kernel(
     Geo g, int Nmax, int Tmax, const float* __restrict__ wav, int ld, const int* __restrict__ n_samples,
     const float* __restrict__ table, float* __restrict__ ws_log) {
@@ -279,7 +277,7 @@ __global__ __launch_bounds__(NT) void cmvn_accumulate_kernel(
   for (int b = 0; b < B; ++b) {
     const int id = spk[b];  // uniform
     if (id < 0 || id >= S) {
-      if (s == 0 && tid == 0) atomicOr(err, 1);
+      if (s == 0 && tid == 0) atomicOr(err, MLVAE_CMVN_ERR_SPEAKER);
       continue;
     }
     if (id != s) continue;
@@ -317,13 +315,13 @@ __global__ __launch_bounds__(NT) void cmvn_apply_kernel(
   if (t0 >= Tb) return;  // uniform
   const int id = spk[b];
   if (id < 0 || id >= S) {
-    if (tid == 0) atomicOr(err, 1);
+    if (tid == 0) atomicOr(err, MLVAE_CMVN_ERR_SPEAKER);
     return;
   }
   const double* row = stats + (size_t)id * (2 * D + 1);
   const double n = row[2 * D];
   if (!(n > 0.0)) {  // a speaker nothing was accumulated for
-    if (tid == 0) atomicOr(err, 2);
+    if (tid == 0) atomicOr(err, MLVAE_CMVN_ERR_NO_STATS);
     return;
   }
   const int t1 = t0 + CMVN_ROWS < Tb ? t0 + CMVN_ROWS : Tb;

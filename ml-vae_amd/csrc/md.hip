@@ -67,10 +67,10 @@ __global__ __launch_bounds__(PB) void phn_bce_kernel(int T, int C, const float* 
     int c = -1;
     if (t < Ti) {
       if (idx < 0 || idx >= Li || idx >= L) {
-        bad |= 2;  // no boundary at frame 0, or more boundaries than phonemes
+        bad |= MLVAE_ERR_MD_SEGMENTS;  // no boundary at frame 0, or more boundaries than phonemes
       } else {
         const long long p = phn[(size_t)b * L + idx];
-        if (p < 0 || p >= C) bad |= 4;  // one_hot(num_classes = C) would raise
+        if (p < 0 || p >= C) bad |= MLVAE_ERR_MD_CLASS;  // one_hot(num_classes = C) would raise
         else c = (int)p;
       }
     }
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(PB) void phn_bce_kernel(int T, int C, const float* 
     }
     __syncthreads();  // cls / wsum / carry reused by the next chunk
   }
-  if (tid == 0 && carry_s != Li) bad |= 2;  // boundary count != L_i (phoneme_recognizer.py:65)
+  if (tid == 0 && carry_s != Li) bad |= MLVAE_ERR_MD_SEGMENTS;  // boundary count != L_i (phoneme_recognizer.py:65)
   if (bad) atomicOr(err, bad);
 }
 

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void pi_nll_kernel(size_t n, const float2* __r
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
     const float2 l = logits[i];
     int k = labels[i];
-    if (k < -1 || k > 1) { bad = 32; k = 0; }  // Categorical.log_prob raises for it
+    if (k < -1 || k > 1) { bad = MLVAE_ERR_PI_LABEL; k = 0; }  // Categorical.log_prob raises for it
     if (k < 0) k = 0;                          // past T_i: pad_sequence's zero fill
     // e = exp(min - max): the maximum subtracted before the exponential
     const float e = expf(-fabsf(l.y - l.x));

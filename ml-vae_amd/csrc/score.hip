@@ -21,13 +21,6 @@ namespace {
 constexpr int ST = 256;                  // threads
 constexpr int SW = ST / 64;              // waves
 constexpr int TOPK_MAX_T = 12288;        // frames of one row kept in LDS (48 KB of keys)
-constexpr int SCORE_ERR_SEGMENTS = 128;  // bit of *err: the flags do not give L_b segments from frame 0
-constexpr int SCORE_ERR_K = 256;         // bit of *err: k_b > T_b
-
-__device__ __forceinline__ int round_len(float rel, int n) {
-  int r = (int)rintf((float)n * rel);
-  return r < 0 ? 0 : (r > n ? n : r);
-}
 
 // torch.argmax's order: a NaN is the maximum, the first maximal index wins
 __device__ __forceinline__ bool beats(float x, float best) {
@@ -84,7 +77,7 @@ __global__ __launch_bounds__(ST) void phn_acc_kernel(
     // the reference's asserts: one flag per phoneme, durations that cover [0, T_b)
     const bool good = nf == Li && Ti > 0 && bnd[0] == 1.f;
     if (!good) {
-      if (tid == 0) atomicOr(err, SCORE_ERR_SEGMENTS);
+      if (tid == 0) atomicOr(err, MLVAE_ERR_SCORE_SEGMENTS);
     } else {
       const long long* pt = plvl_tgt + (size_t)b * L;
       int run = 0, hit = 0;  // run: flags before this chunk of ST frames (uniform)
@@ -151,7 +144,7 @@ __global__ __launch_bounds__(ST) void boundary_topk_kernel(
   for (int t = Ti + tid; t < T; t += ST) out[t] = -1;
   if (tid == 0) {
     k_out[b] = k;
-    if (k > Ti) atomicOr(err, SCORE_ERR_K);  // torch.topk raises; the row gets no ones
+    if (k > Ti) atomicOr(err, MLVAE_ERR_SCORE_K);  // torch.topk raises; the row gets no ones
   }
   if (k > Ti) k = 0;
   __syncthreads();

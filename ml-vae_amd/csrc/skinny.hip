@@ -22,12 +22,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) bf16x4* lds_b4_p;
-
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
 template <int NT>  // NB = 16 * NT
 __global__ __launch_bounds__(256) void skinny_nt_kernel(int M, int K, const unsigned short* __restrict__ A,
                                                         int lda, const unsigned short* __restrict__ Bt,

@@ -11,6 +11,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 CSRC = os.path.join(PKG, "csrc")
+# the device error words' bits: csrc/common.h includes it from the public include directory
+ERR_H = os.path.join(os.path.dirname(PKG), "include", "mlvae_err.h")
 OUT = os.path.join(HERE, "libmlvae.so")
 # --diag: the diagnostics build (MLVAE_DIAG: recurrence phase stamps and debug-mode timing
 # variants, csrc/lstm_common.h) -> libmlvae_diag.so, loaded by the tools through MLVAE_LIB_PATH
@@ -29,7 +31,7 @@ def _stale(src, diag=False):
     o = _obj(src, diag)
     if not os.path.exists(o):
         return True
-    deps = [os.path.join(CSRC, src)] + glob.glob(os.path.join(CSRC, "*.h"))
+    deps = [os.path.join(CSRC, src)] + glob.glob(os.path.join(CSRC, "*.h")) + [ERR_H]
     return any(os.path.getmtime(d) > os.path.getmtime(o) for d in deps)
 
 

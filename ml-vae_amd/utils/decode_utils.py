@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from mlvae_hip._lib import check, lib
+from mlvae_hip.ops import errors
 
 
 def _f32(t, dev):
@@ -58,8 +59,9 @@ def decode_md_device(predictions, feat_lens, plvl_cnnl_seqs, plvl_cnnl_seq_lens,
 
 
 def raise_decode_err(code):
-    if int(code):
-        raise AssertionError(f"MD decode: backtrack did not end at (0, 0) / empty utterance (err {int(code)})")
+    exc, _ = errors.read(int(code), "decode")  # the decode's own word: nothing to clear
+    if exc is not None:
+        raise exc
 
 
 def decoded_lists(bnd, flvl, plvl, lens, err):

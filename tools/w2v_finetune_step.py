@@ -125,8 +125,9 @@ def main():
                 events.append((FAMILIES[name], e0, e1))
         return inner
     saved = {n: getattr(ops, n) for n in FAMILIES}
-    for n, fn in saved.items():
-        setattr(ops, n, wrap(n, fn))
+    for n, fn in saved.items():  # the module's calls go through ops., the autograd pieces' through ops.w2v
+        for where in (ops, ops.w2v):
+            setattr(where, n, wrap(n, fn))
     try:
         fam = {}
         for _ in range(3):
@@ -145,7 +146,8 @@ def main():
             stat("family: " + f, fam[f], out, calls=calls[f], **meta)
     finally:
         for n, fn in saved.items():
-            setattr(ops, n, fn)
+            for where in (ops, ops.w2v):
+                setattr(where, n, fn)
 
 
 if __name__ == "__main__":
