@@ -11,7 +11,8 @@
 // B = 256 (HJ 64): the per-step MFMA work of a workgroup grows 2-4x while the serial hand-off
 // chain -- the recurrence's real bound -- is paid once per layer instead of once per chunk.
 //
-// Workgroup = 8 waves (512 threads, one per CU: the VGPR file is full).
+// Workgroup = 8 waves (512 threads, one per CU: the VGPR file is full); the forward's default
+// is its 12-wave form (W12 below: waves 0-7 own the tiles and poll, waves 8-11 move the data).
 //   forward:  gates^T[4HJ x 16] = W_hh[rows of my units] . h_{t-1}^T.  Wave w owns TPW M-tiles
 //             (16 gate rows = 4 units x i,f,g,o) as resident A-fragments for all of K = H;
 //             lane (utt, q) ends with the 4 gates of one unit -> in-register cell update.
@@ -76,7 +77,8 @@ __device__ __forceinline__ int swz(int utt, int slot) { return slot ^ (utt & 15)
 // tiles of each SIMD and the io waves only move data: their DMA and stores right behind the
 // barrier, inside the pollers' MFMA / cell phase.  Same box, in the step: forward per launch
 // c2 0.954 -> 0.863, c5 (B = 64) 0.979 -> 0.872, c4 3.95 -> 3.49 ms (profiles/ab/r04_as.txt);
-// the only form at TPW 1 since round 6.  At TPW 2 the pollers' 3 tiles spilled 46 VGPRs.
+// the only form at TPW 1 since round 6.  At TPW 2 in 8 waves the pollers' 3 tiles spilled 46
+// VGPRs; there the split exists in 12 waves only (W12 below).
 // ZP: the layer-0 input projection fused (a.Zb): io wave 4 DMAs the step's 16 z rows (64 B each)
 // into the gx ring's space and each tile's gate inputs are one v_mfma_f32_16x16x32_bf16 of the
 // resident W_ih fragment (K = 32 = the latent width) onto the tile's b_ih + b_hh -- instead of
@@ -89,15 +91,28 @@ __device__ __forceinline__ int swz(int utt, int slot) { return slot ^ (utt & 15)
 // had issued behind their own publish (profiles/r06_lstm_stamps.txt).  Tile-less io waves issue
 // those stores right behind the barrier instead, a whole step ahead of the wait.  Groups have
 // 16 members (H / 32), two groups per XCD.
-// W12: 12 waves (768 threads, three per SIMD).  Waves 0-7 each own ONE M-tile (4 units) across
-// the NT N-tiles -- its W_hh A-fragments all in registers (64 VGPRs, under the 168 a wave gets at
-// three per SIMD) -- and all eight poll; waves 8-11 only move data.  Every SIMD keeps two MFMA
-// waves (one's cell overlaps the other's MFMAs) beside a tile-less io wave.
+// W12: 12 waves (768 threads, three per SIMD).  Waves 0-7 each own TPW M-tiles (4 units each)
+// across the NT N-tiles and all eight poll; waves 8-11 only move data.  Every SIMD keeps two MFMA
+// waves (one's cell overlaps the other's MFMAs) beside a tile-less io wave.  At TPW 1 a wave's
+// W_hh A-fragments are all in registers (64 VGPRs, under the 168 a wave gets at three per SIMD).
+// At TPW 2 (W2: B = 256, 16 utterances x 64 units, two tiles and one 16-byte publish per wave)
+// 12 of the 16 k-chunks are resident (96 VGPRs) and the rest of the wave has to fit in 72, with
+// no scratch -- what it took, beside FWD_KLF = 4 chunks in LDS as in the 8-wave TPW-2 form:
+//   - the h read-ahead is 2 k-chunks per batch (HB), and the LDS-resident fragments are read with
+//     the batch that multiplies them (16 registers live) instead of all 32 at the first batch;
+//   - the 16 swizzled h-image addresses of a row come from four bases (hsw);
+//   - the prologue converts W_hh to bf16 eight k-chunks at a time (load_w);
+//   - ZP: W_ih's fragments and the bias quads live in LDS, in the gx ring's place (GXB), and tile
+//     t's z projection is issued with register batch t, where no LDS fragment is live.
+// Each tile's accumulation order over the k-chunks (12 .. 15, 0 .. 11) and the cell math are the
+// 8-wave TPW-2 form's: every output is the same bits (tests/test_gpu_lstm_wide_w12.py).
 template <int TPW, int NKC, int OCC, bool DBG = false, bool AS = false, bool ZP = false, int NT = 1,
           bool W12 = false>
 __global__ __launch_bounds__(W12 ? 768 : 512, W12 ? 1 : OCC) void lstm_fwd_wide_kernel(LstmArgs a) {
   static_assert(NT == 1 || (NT == 2 && AS && TPW == 1), "two N-tiles: the asymmetric TPW-1 split");
-  static_assert(!W12 || (AS && TPW == 1), "12 waves: the asymmetric TPW-1 split");
+  static_assert(!W12 || AS, "12 waves: tile-less io waves");
+  static_assert(!W12 || TPW == 1 || NT == 1, "12 waves at TPW 2: one N-tile");
+  constexpr bool W2 = W12 && TPW == 2;        // 12 waves, two M-tiles per MFMA wave
   constexpr int NWV = W12 ? 12 : 8;           // waves per workgroup
   constexpr int NPOLL = W12 ? 8 : 4;          // polling waves (0 .. NPOLL-1)
   constexpr int IO0 = NWV - 4;                // first io wave
@@ -112,9 +127,9 @@ __global__ __launch_bounds__(W12 ? 768 : 512, W12 ? 1 : OCC) void lstm_fwd_wide_
   constexpr int OUB = 4 * HJ * 2 + 2 * HJ * 4 + 16;
   constexpr int NC8 = BGW * HJ / 8;           // 8-unit chunks of h per step
   // k-chunks whose A-fragments live in LDS (VGPR budget; at TPW 1 one tile's 16 fit in registers)
-  constexpr int KLF = ((TPW == 1 && !AS) || W12) ? 0 : FWD_KLF;
+  constexpr int KLF = ((TPW == 1 && !AS) || (W12 && TPW == 1)) ? 0 : FWD_KLF;
   constexpr int KR = NKC - KLF;               // ... and in registers
-  constexpr int HB = 4;                       // B-fragments (h) read ahead per batch
+  constexpr int HB = W2 ? 2 : 4;              // B-fragments (h) read ahead per batch
   constexpr int NQ = 16 * 4 * HJ / 4;         // 16-byte quads of gx / gates per step
   constexpr int QPT = NQ / 256;               // quads per io thread
   static_assert(NQ % 256 == 0, "io split");
@@ -123,7 +138,9 @@ __global__ __launch_bounds__(W12 ? 768 : 512, W12 ? 1 : OCC) void lstm_fwd_wide_
   RTS_DECL;
   char* himg = smem;                                        // [2][BGW][ROWB], swizzled slots
   unsigned short* gxr = reinterpret_cast<unsigned short*>(smem + 2 * HIMG);  // [2][BGW][GXU] fp16
-  char* outr = reinterpret_cast<char*>(gxr + 2 * BGW * GXU);                // [2][BGW][OUB]
+  // (W2 with ZP: z rows, bias quads and W_ih fragments instead of the ring -- wide_lds())
+  constexpr int GXB = (W2 && ZP) ? 2 * BGW * 32 * 2 + WW * TPW * (4 * 16 + 64 * 16) : 2 * BGW * GXU * 2;
+  char* outr = reinterpret_cast<char*>(gxr) + GXB;                          // [2][BGW][OUB]
   bf16x8* wlds = reinterpret_cast<bf16x8*>(outr + 2 * BGW * OUB);  // [wave][TPW][KLF][lane]
   unsigned* dbl = reinterpret_cast<unsigned*>(wlds + 8 * TPW * KLF * 64);  // [2][NC8] keep bits
   __shared__ int abort_flag;
@@ -148,8 +165,8 @@ __global__ __launch_bounds__(W12 ? 768 : 512, W12 ? 1 : OCC) void lstm_fwd_wide_
 
   // tiles per poller / io wave (AS) and a wave's first tile
   // (TPW 2 as 3 + 1 spilled 46 VGPRs: the split applies to TPW 1 only)
-  static_assert(!AS || TPW == 1, "asymmetric split: TPW 1 only");
-  constexpr int TPP = W12 ? 1 : AS ? 2 : TPW;
+  static_assert(!AS || TPW == 1 || W12, "asymmetric split in 8 waves: TPW 1 only");
+  constexpr int TPP = W12 ? TPW : AS ? 2 : TPW;
   constexpr int TPI = AS ? 0 : TPW;
   static_assert(NPOLL * TPP + 4 * TPI == WW * TPW, "every tile owned once");
   // resident A-fragments: tile m, row r = bi -> unit 4m + (r >> 2), gate r & 3; k-chunks
@@ -167,6 +184,13 @@ __global__ __launch_bounds__(W12 ? 768 : 512, W12 ? 1 : OCC) void lstm_fwd_wide_
         for (int e = 0; e < 4; ++e) { v[e] = f2bf(w0[e]); v[4 + e] = f2bf(w1[e]); }
         if (kc < KR) wreg[t][kc < KR ? kc : 0] = v;
         else wlds[(m * KLF + (kc - KR)) * 64 + lane] = v;
+        // (W2: at most 8 k-chunks' fp32 rows in flight, and converted here -- issued all at once,
+        // or the conversions sunk into the step loop's preheader, a tile's raw rows spilled beside
+        // the 96 resident fragment registers)
+        if constexpr (W2) {
+          if (kc < KR) asm volatile("" : "+v"(wreg[t][kc < KR ? kc : 0]));
+          if (kc % 8 == 7) __builtin_amdgcn_sched_barrier(0);
+        }
       }
     }
   };
@@ -200,6 +224,10 @@ __global__ __launch_bounds__(W12 ? 768 : 512, W12 ? 1 : OCC) void lstm_fwd_wide_
   const auto rgx_abs = make_rsrc(G16, (unsigned)min((size_t)a.B * T * 8 * H * 2, (size_t)0xffffffffu));
   // ZP: z rows [16 utt][32] bf16 per ring slot, lane-linear (lane 4 u + c: 16 B chunk c of utt u)
   unsigned short* zr = gxr;
+  // ZP in 12 waves at TPW 2: behind the z rows, b_ih + b_hh as [tile][q] quads in the accumulator
+  // layout and the W_ih fragments [tile][lane] (16 VGPRs a wave does not have to hold)
+  f32x4* bzl = reinterpret_cast<f32x4*>(zr + 2 * BGW * 32);
+  bf16x8* wzl = reinterpret_cast<bf16x8*>(bzl + WW * TPW * 4);
   const auto rz = make_rsrc(a.Zb, (unsigned)min((size_t)a.B * T * a.ldz * 2, (size_t)0x7fffffff));
   auto io_load = [&](int s_) {  // input projection of step s_ into gx ring slot s_ & 1
     if (s_ >= T || (s_ > 0 && (DMODE(a) & 8192))) return;  // bit 13: timing without the loads
@@ -341,6 +369,11 @@ __global__ __launch_bounds__(W12 ? 768 : 512, W12 ? 1 : OCC) void lstm_fwd_wide_
         for (int e = 0; e < 4; ++e) { wz[t][e] = f2bf(w0[e]); wz[t][4 + e] = f2bf(w1[e]); }
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) bz4[t][g4] = bih[g4 * H + j0 + 4 * m + q] + bhh[g4 * H + j0 + 4 * m + q];
+        // W2: both live in LDS (complete at the barrier below) and are read with the z rows
+        if constexpr (W2) {
+          wzl[m * 64 + lane] = wz[t];
+          if (bi == 0) bzl[4 * m + q] = bz4[t];
+        }
       }
     }
     // AS with tile-less io waves: their DMA and stores right behind the barrier
@@ -356,6 +389,12 @@ __global__ __launch_bounds__(W12 ? 768 : 512, W12 ? 1 : OCC) void lstm_fwd_wide_
     for (int t = 0; t < MTA; ++t)
 #pragma unroll
       for (int n = 0; n < NT; ++n) c[t][n] = 0.f;
+    // W2: the swizzle touches slot bits 0-3 only, swz(bi, 4 kc + q) = 16 (kc >> 2) + ((4 (kc & 3)
+    // + q) ^ bi), so the 16 B-fragment addresses of a row are four bases plus a constant -- 4
+    // VGPRs where the compiler, not seeing through the XOR, held 16
+    int hsw[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) hsw[j] = bi * ROWB + swz(bi, 4 * j + q) * 16;
     stagger_start(gid, DMODE(a));
     for (int s = 0; s < T; ++s) {
       LSTAMP(0);
@@ -380,7 +419,11 @@ __global__ __launch_bounds__(W12 ? 768 : 512, W12 ? 1 : OCC) void lstm_fwd_wide_
               const bf16x8 zf = *reinterpret_cast<const bf16x8*>(zr + ((s & 1) * BGW + 16 * n + bi) * 32 + 8 * q);
 #pragma unroll
               for (int t = 0; t < MT; ++t) {
-                const f32x4 r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wz[t], zf, bz4[t], 0, 0, 0);
+                f32x4 r;
+                if constexpr (W2)  // (W_ih fragments and bias quads in LDS)
+                  r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wzl[(m0 + t) * 64 + lane], zf, bzl[4 * (m0 + t) + q], 0, 0, 0);
+                else
+                  r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wz[t], zf, bz4[t], 0, 0, 0);
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) gxv[t][n][g4] = r[g4];
               }
@@ -480,17 +523,45 @@ __global__ __launch_bounds__(W12 ? 768 : 512, W12 ? 1 : OCC) void lstm_fwd_wide_
         // reads right behind the barrier, where one LDS round trip is exposed anyway -- read
         // inside the chain they had one or two MFMAs of cover each
         constexpr int KLA = KLF > 0 ? KLF : 1;
-        bf16x8 wl[MTA][KLA];
+        // (W2: HB of them at a time, read with the batch that uses them -- all KLF fragments of
+        // both tiles at once are 32 VGPRs the 168-register wave does not have)
+        bf16x8 wl[MTA][W2 ? HB : KLA];
         bf16x8 zf[NT];
+        f32x4 bzf;
+        bf16x8 wzf;
+        constexpr int ZK0 = KLF;  // W2 with ZP: the first batch that projects z rows
 #pragma unroll
         for (int k0 = 0; k0 < NKC; k0 += HB) {
           bf16x8 hfrag[HB][NT];
 #pragma unroll
           for (int i = 0; i < HB; ++i)
 #pragma unroll
-            for (int n = 0; n < NT; ++n)
-              hfrag[i][n] = *reinterpret_cast<const bf16x8*>(hb + (16 * n + bi) * ROWB + swz(bi, ((k0 + i + KR) % NKC) * 4 + q) * 16);
-          if (k0 == 0) {
+            for (int n = 0; n < NT; ++n) {
+              const int kc = (k0 + i + KR) % NKC;
+              if constexpr (W2)  // swz(bi, 4 kc + q) * 16 from four bases: see hsw
+                hfrag[i][n] = *reinterpret_cast<const bf16x8*>(hb + hsw[kc & 3] + (kc >> 2) * 256);
+              else
+                hfrag[i][n] = *reinterpret_cast<const bf16x8*>(hb + (16 * n + bi) * ROWB + swz(bi, kc * 4 + q) * 16);
+            }
+          if constexpr (W2) {
+            static_assert(!W2 || KLF % HB == 0, "a batch is all LDS chunks or all register chunks");
+            if (k0 < KLF) {
+#pragma unroll
+              for (int t = 0; t < MT; ++t)
+#pragma unroll
+                for (int i = 0; i < HB; ++i) wl[t][i] = wlds[((m0 + t) * KLF + k0 + i) * 64 + lane];
+            }
+            if constexpr (ZP) {
+              // (tile t's z projection with register batch t, where wl is dead: its W_ih fragment
+              // and bias quad come from LDS with the z rows)
+              if (k0 >= ZK0 && k0 < ZK0 + MT * HB) {
+                const int t = (k0 - ZK0) / HB;
+                zf[0] = *reinterpret_cast<const bf16x8*>(zr + ((s & 1) * BGW + bi) * 32 + 8 * q);
+                bzf = bzl[4 * (m0 + t) + q];
+                wzf = wzl[(m0 + t) * 64 + lane];
+              }
+            }
+          } else if (k0 == 0) {
 #pragma unroll
             for (int t = 0; t < MT; ++t)
 #pragma unroll
@@ -502,7 +573,13 @@ __global__ __launch_bounds__(W12 ? 768 : 512, W12 ? 1 : OCC) void lstm_fwd_wide_
             }
           }
           __builtin_amdgcn_sched_barrier(0);  // the batch's reads issue before its MFMAs
-          if constexpr (ZP) {
+          if constexpr (ZP && W2) {
+            if (k0 >= ZK0 && k0 < ZK0 + MT * HB) {
+              const f32x4 r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wzf, zf[0], bzf, 0, 0, 0);
+#pragma unroll
+              for (int g4 = 0; g4 < 4; ++g4) gxv[(k0 - ZK0) / HB][0][g4] = r[g4];
+            }
+          } else if constexpr (ZP) {
             if (k0 == 0) {
 #pragma unroll
               for (int t = 0; t < MT; ++t)
@@ -519,7 +596,7 @@ __global__ __launch_bounds__(W12 ? 768 : 512, W12 ? 1 : OCC) void lstm_fwd_wide_
             const int kc = (k0 + i + KR) % NKC;
 #pragma unroll
             for (int t = 0; t < MT; ++t) {
-              const bf16x8 wf = kc < KR ? wreg[t][kc < KR ? kc : 0] : wl[t][kc >= KR ? kc - KR : 0];
+              const bf16x8 wf = kc < KR ? wreg[t][kc < KR ? kc : 0] : wl[t][W2 ? i : kc >= KR ? kc - KR : 0];
 #pragma unroll
               for (int n = 0; n < NT; ++n)
                 acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, hfrag[i][n], acc[t][n], 0, 0, 0);
@@ -606,7 +683,7 @@ __global__ __launch_bounds__(W12 ? 768 : 512, W12 ? 1 : OCC) void lstm_fwd_wide_
           // (equal shares: NT = 1, static_assert at the top)
           const int u0 = j0 + 4 * TPW * wave;  // the wave's first unit
           const unsigned cell = (unsigned)((s & nmask) * xslot) + ((u0 >> 3) * 16 + bi) * 8 + (u0 & 7);
-          if constexpr (TPW == 2) {
+          if constexpr (TPW == 2 && !AS) {
             const u32x4 v = {(unsigned)gr[0][0], (unsigned)(gr[0][0] >> 32), (unsigned)gr[1][0], (unsigned)(gr[1][0] >> 32)};
             if (same_xcd) __builtin_amdgcn_raw_buffer_store_b128(v, xr, cell * sizeof(short), 0, 0);
             else st_sc1_b128(xr, cell * sizeof(short), v);
@@ -1185,10 +1262,14 @@ int wide_cus() {
   return cus;
 }
 
-size_t wide_lds(int H, int hj, bool fwd, int nt = 1) {
+// zp2: the 12-wave TPW-2 forward with the fused z projection -- z rows, bias quads and W_ih
+// fragments (lstm_fwd_wide_kernel GXB) in the gx ring's place
+size_t wide_lds(int H, int hj, bool fwd, int nt = 1, bool zp2 = false) {
   const size_t bgw = (size_t)BG * nt;
   if (fwd)
-    return 2 * bgw * H * 2 + 2 * bgw * (4 * hj + 8) * 2 +  // h image, gx ring
+    return 2 * bgw * H * 2 +                                // h image
+           (zp2 ? 2 * bgw * 32 * 2 + (size_t)8 * (hj / 32) * (4 * 16 + 64 * 16)
+                : 2 * bgw * (4 * hj + 8) * 2) +             // gx ring
            2 * bgw * (4 * hj * 2 + 2 * hj * 4 + 16) +      // out ring
            (size_t)8 * (hj / 32) * FWD_KLF * 64 * 16 +     // + the LDS-resident A-fragments
            2 * (bgw * hj / 8) * 4;                         // + dropout keep bits
@@ -1198,13 +1279,14 @@ size_t wide_lds(int H, int hj, bool fwd, int nt = 1) {
 }
 
 // mode bits (mlvae_lstm_set_debug_mode, A/B): 9 -- past B = 64 the forward takes the 32-utterance
-// form (NT = 2) instead of TPW 2 (16 utterances x 64 units per workgroup); 11 -- the TPW-1 forward
-// in 8 waves (4 pollers with two M-tiles each + 4 io waves) instead of 12.
+// form (NT = 2) instead of TPW 2 (16 utterances x 64 units per workgroup); 11 -- the forward in
+// 8 waves instead of 12 (TPW 1: 4 pollers with two M-tiles each + 4 io waves; TPW 2: equal shares,
+// every wave owning two tiles).
 // Same box, in the step (profiles/ab/r06_fwd_w12.txt): c2 forward 0.84 -> 0.74 ms per launch with
 // 12 waves (step 4.10 -> 3.90 ms); at c3 NT = 2 runs 1.25 ms in 12 waves, 1.48 in 8, against TPW 2's
 // 1.17 -- its h image is twice as large, and every MFMA wave reads all of it (256 vs 192 KB of LDS
 // reads per CU per step)
-WidePlan wide_plan(int B, int H, bool fwd, int mode = 0) {
+WidePlan wide_plan(int B, int H, bool fwd, int mode = 0, bool zp = false) {
   WidePlan p{};
   p.ok = false;
   p.nt = 1;
@@ -1239,14 +1321,17 @@ WidePlan wide_plan(int B, int H, bool fwd, int mode = 0) {
     }
   }
   if (!p.ok) return p;
-  // (TPW 2 in 12 waves -- 2 M-tiles per MFMA wave -- spills 65-117 VGPRs past the 168 a wave has
-  // at three per SIMD: W_hh's resident 12 k-chunks alone take 96, and LDS has room for no more.
-  // The BPTT in 12 waves at TPW 1 -- 8 compute waves, 4 io waves staging the cell inputs and
+  // The forward takes 12 waves at both TPW (bit 11: 8 waves).  TPW 2 in 12 waves -- 2 M-tiles per
+  // MFMA wave, W_hh's 12 resident k-chunks alone 96 of the 168 VGPRs a wave has at three per SIMD
+  // -- fits without scratch since the register diet in the kernel's header comment (W12).  Same
+  // box, alternating, in the step (profiles/ab/r07_fwd_w12_tpw2.txt): c3 forward 1.245 -> 1.204 ms
+  // per launch, step 9.42 -> 9.28 ms.
+  // (The BPTT in 12 waves at TPW 1 -- 8 compute waves, 4 io waves staging the cell inputs and
   // storing dG -- measured slower, 0.86 -> 0.97 ms per launch at c2 with the io traffic right
   // behind the step barrier (it queued ahead of the compute waves' publish), 1.0 ms with it held
   // until every compute wave had polled (the barrier then waited for the io waves).)
-  if (fwd && p.tpw == 1) p.w12 = !(mode & 2048);
-  p.lds = wide_lds(H, p.HJ, fwd, p.nt);
+  if (fwd) p.w12 = !(mode & 2048);
+  p.lds = wide_lds(H, p.HJ, fwd, p.nt, zp && p.w12 && p.tpw == 2);
   if (fwd) p.xbytes = (size_t)2 * p.NB * NSLOT * BG * p.nt * H * 2;
   else p.xbytes = (size_t)2 * p.NB * NSLOT * p.NJ * p.NJ * p.HJ * 16 * 2;
   if (p.lds < (size_t)MIN_LDS) p.lds = MIN_LDS;  // one recurrence workgroup per CU (residency)
@@ -1261,16 +1346,16 @@ int launch_wide(bool fwd, const LstmArgs& a, const WidePlan& p, hipStream_t s) {
   // train step's form (bf16 dY, no fp8 copy)
   const bool dbg = a.dbg != nullptr;
   // the forward at TPW 1 always takes the asymmetric split (the equal-shares form, debug bit 8
-  // through round 5, was retired in round 6); TPW 2 keeps equal shares
+  // through round 5, was retired in round 6); TPW 2 has equal shares in 8 waves (bit 11) only
   constexpr bool AS1 = TPW == 1;
   const bool zp = a.Zb != nullptr;          // fused layer-0 projection (checked: no DBG with it)
   auto k = (fwd && p.w12)
                ? (p.nt == 2 ? (dbg ? lstm_fwd_wide_kernel<1, NKC, OCC, true, true, false, 2, true>
                                    : zp ? lstm_fwd_wide_kernel<1, NKC, OCC, false, true, true, 2, true>
                                         : lstm_fwd_wide_kernel<1, NKC, OCC, false, true, false, 2, true>)
-                            : (dbg ? lstm_fwd_wide_kernel<1, NKC, OCC, true, true, false, 1, true>
-                                   : zp ? lstm_fwd_wide_kernel<1, NKC, OCC, false, true, true, 1, true>
-                                        : lstm_fwd_wide_kernel<1, NKC, OCC, false, true, false, 1, true>))
+                            : (dbg ? lstm_fwd_wide_kernel<TPW, NKC, OCC, true, true, false, 1, true>
+                                   : zp ? lstm_fwd_wide_kernel<TPW, NKC, OCC, false, true, true, 1, true>
+                                        : lstm_fwd_wide_kernel<TPW, NKC, OCC, false, true, false, 1, true>))
          : (fwd && p.nt == 2)
                ? (dbg ? lstm_fwd_wide_kernel<1, NKC, OCC, true, true, false, 2>
                       : zp ? lstm_fwd_wide_kernel<1, NKC, OCC, false, true, true, 2>
@@ -1318,7 +1403,7 @@ int lstm_wide_run(bool fwd, int B, int T, int H, const float* W0, const float* W
                   unsigned long long dseed, unsigned long long doff, float dp,
                   unsigned long long* dbg, int dbg_mode, const WideFp8& f8, const unsigned short* dyb,
                   const WideZ& wz) {
-  WidePlan p = wide_plan(B, H, fwd, dbg_mode);
+  WidePlan p = wide_plan(B, H, fwd, dbg_mode, fwd && wz.zb != nullptr);
   if (!p.ok) return -1;
   // the kernels address a batch group's rows through one buffer descriptor (32-bit offsets)
   if (!lstm_wide_t_ok(T, H)) {
