@@ -62,10 +62,18 @@ int mlvae_gemm_ex_drop(int trans_a, int trans_b, int M, int N, int K, float alph
  * A_b = A + b*a_bstride (elements; strides may be negative), likewise B_b, C_b.  trans_a = 0: A [M,K] k-contiguous;
  * trans_a = 1: A stored [K,M].  trans_b = 1: B stored [N,K]; trans_b = 0: B stored [K,N].
  * kshift (+ b*kshift_bstep) time-shifts the rows of a [K,N] B operand as mlvae_gemm does.
- * epi as mlvae_gemm_ex_drop (3 = dropout mask of (drop_seed, row*ldc + col)); epi | 16
+ * epi as mlvae_gemm_ex_drop; 3 = dropout: C[row, col] of EVERY batch entry is multiplied by the
+ * mlvae_dropout_ex mask of element drop_offset + row*ldc + col (ldc in elements of C; the index
+ * does not depend on the batch entry).  drop_offset must be a multiple of 4 (the vector epilogues
+ * take one mask quad per 4 columns); any other value is refused with status 1.  epi | 16
  * (EPI_OUT_F16) stores C as IEEE fp16 (C then points at fp16; beta 0, epi 0 or 3, N, ldc and
  * c_bstride multiples of 4 / 8, aligned C and biases): the input projection into the wide
- * recurrence's fp16 gate buffer (mlvae_lstm_gates_fp16).  Operands need
+ * recurrence's fp16 gate buffer (mlvae_lstm_gates_fp16).  epi | 32 (EPI_OUT_BF16) stores C as
+ * bf16 (round to nearest even) under the same conditions with epi 0, 1 (LeakyReLU) or 3 (dropout):
+ * the wav2vec2 layers' activations and the wide BPTT's dY; with N and ldc multiples of 8 a lane
+ * stores 8 columns, else 4.  ldc and c_bstride count elements of C's type.  A 16-bit C with
+ * beta != 0, another epilogue, N or ldc % 4 != 0, c_bstride % 8 != 0, or C / bias1 / bias2 off a
+ * 16-byte boundary is refused with status 1 and C untouched.  Operands need
  * 16-byte aligned bases, lda/ldb and the contiguous extent multiples of 8.  Long-K products
  * split K into fp32 partial slabs (workspace: mlvae_gemm_bf16_workspace_size) reduced in a fixed
  * order.  Replaces the LSTM input projection, its dgrad and the weight gradients
@@ -407,7 +415,8 @@ int mlvae_gmm_latent_fwd_rows(int B, int T, int N, int Z, const float* P, int ld
 int mlvae_gemm_fp8(int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
                    const float* alpha, const float* bias1, const float* bias2, int epi, void* stream);
 /* As mlvae_gemm_fp8 with epi = EPI_DROPOUT allowed (fp32 or, with the EPI_OUT_BF16 flag 32, bf16
- * C): C *= the inter-layer dropout mask of element drop_offset + row * ldc + col -- the fp8
+ * C): C *= the inter-layer dropout mask of element drop_offset + row * ldc + col (drop_offset a
+ * multiple of 4, as mlvae_gemm_bf16: any other value is refused) -- the fp8
  * layer-1 dgrad with the dropout backward fused (ref:src/modules/decoder.py:14-15: the dropout
  * between the LSTM layers); bf16 C is the wide BPTT's dY input (mlvae_lstm_bwd_ex3). */
 int mlvae_gemm_fp8_ex(int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C,

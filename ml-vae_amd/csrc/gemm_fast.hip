@@ -1176,6 +1176,12 @@ extern "C" int mlvae_gemm_bf16(int trans_a, int trans_b, int M, int N, int K, in
     mlvae_set_error("mlvae_gemm_bf16: dropout p=%f out of range", drop_p);
     return 1;
   }
+  // the vector epilogues take one mask quad (4 consecutive elements of the mask stream) per 4
+  // columns: the quad of doff + row*ldc + col is the lane's own only for doff % 4 == 0
+  if (epi == EPI_DROPOUT && drop_offset % 4 != 0) {
+    mlvae_set_error("mlvae_gemm_bf16: drop_offset %llu is not a multiple of 4", drop_offset);
+    return 1;
+  }
   if ((kshift != 0 || kshift_bstep != 0) && (trans_b || kshift_T <= 0)) {
     mlvae_set_error("mlvae_gemm_bf16: kshift needs trans_b = 0, T > 0");
     return 1;
@@ -1384,6 +1390,10 @@ extern "C" int mlvae_gemm_fp8_ex(int M, int N, int K, const void* A, int lda, co
       (epi == EPI_DROPOUT && (c16 == 1 || !(drop_p >= 0.f && drop_p < 1.f)))) {
     mlvae_set_error("mlvae_gemm_fp8: epilogue none (+ fp16 / bf16 C) or dropout (fp32 / bf16 C), N and ldc %% 4, "
                     "aligned C / bias");
+    return 1;
+  }
+  if (epi == EPI_DROPOUT && drop_offset % 4 != 0) {  // one mask quad per 4 columns (as mlvae_gemm_bf16)
+    mlvae_set_error("mlvae_gemm_fp8: drop_offset %llu is not a multiple of 4", drop_offset);
     return 1;
   }
   if (((uintptr_t)A % 16) || ((uintptr_t)B % 16) || (lda % 16) || (ldb % 16) || (K % 16)) {

@@ -3,21 +3,11 @@ and the epilogues, against an fp64 product of the same bf16 operands."""
 import pytest
 import torch
 
+from gemm_fast_ref import _shift_rows
 from gpu_utils import P, need_gpu, rel_err, stream
 from mlvae_hip._lib import check, lib
 
 pytestmark = pytest.mark.gpu
-
-
-def _shift_rows(b, T, shift):
-    """rows k of B -> k + shift when 0 <= k % T + shift < T, else zero (the recurrent dW_hh)."""
-    K = b.shape[0]
-    t = torch.arange(K) % T + shift
-    ok = (t >= 0) & (t < T)
-    idx = torch.arange(K) + shift
-    out = torch.zeros_like(b)
-    out[ok] = b[idx[ok]]
-    return out
 
 
 def _run(ta, tb, M, N, K, batch=1, kshift_T=0, kshift=0, kstep=0, epi=0, beta=0.0, bias=True,
