@@ -106,6 +106,12 @@ __device__ __forceinline__ int swz(int utt, int slot) { return slot ^ (utt & 15)
 //     t's z projection is issued with register batch t, where no LDS fragment is live.
 // Each tile's accumulation order over the k-chunks (12 .. 15, 0 .. 11) and the cell math are the
 // 8-wave TPW-2 form's: every output is the same bits (tests/test_gpu_lstm_wide_w12.py).
+// Measured and dropped at W2 (profiles/ab/r08_fwd_kphases.txt): two K-phases per step -- waves 0-3
+// gather chunks 12 .. 15, 0 .. 3, a first barrier, waves 4-7 gather 4 .. 11 under their phase-1
+// MFMAs, a second barrier.  The first half of that order holds four odd chunks, which the producers'
+// second MFMA waves publish ~900 ticks after the even ones, so barrier 1 came no earlier than the
+// single barrier's early pollers and the step paid a second barrier (forward +0.12 ms per launch
+// against the single barrier in the same build).  An even-chunks-first order is the open variant.
 template <int TPW, int NKC, int OCC, bool DBG = false, bool AS = false, bool ZP = false, int NT = 1,
           bool W12 = false>
 __global__ __launch_bounds__(W12 ? 768 : 512, W12 ? 1 : OCC) void lstm_fwd_wide_kernel(LstmArgs a) {
@@ -466,19 +472,32 @@ __global__ __launch_bounds__(W12 ? 768 : 512, W12 ? 1 : OCC) void lstm_fwd_wide_
           // ms/step; at c2's 128 workgroups full sweeps with s_sleep 6 stay 1 % faster).  A/B
           // bit 28: full re-loads with s_sleep 6 at every size; bit 30: s_sleep 1
           const bool partial = (int)gridDim.x >= 256 && !(DMODE(a) & (1 << 28));
+          // diagnostics (slots 8 + wave; debug bits 21-22 select): when the wave starts its first
+          // sweep (1), when its first / second k-chunk first carries the step's tag (2 / 3)
+          const int wsel = DBG ? (DMODE(a) >> 21) & 3 : 0;
+          unsigned long long wtk[3] = {0, 0, 0};
+          if (DBG && wsel) wtk[0] = __builtin_amdgcn_s_memtime();
+          // The first sweep loads every chunk, back to back and without a test.  (It used to run
+          // through the retry sweep's per-chunk "is this one stale" branches on registers preset to
+          // a stale tag: some forty scalar instructions and two branches in front of, and between,
+          // the loads every later stage of the step waits for -- profiles/ab/r08_fwd_kphases.txt.)
 #pragma unroll
-          for (int i = 0; i < PLN; ++i) hv[i] = u32x4{tag ^ 1u, 0u, tag ^ 1u, 0u};  // stale: first sweep loads all
+          for (int i = 0; i < PLN; ++i) hv[i] = ld_sc1_b128(xr, poll_off(i) * sizeof(short));
+          // step s-1's dropout keep bits, drawn while the first poll's loads are in flight
+          // (drawn before them, at the end of step s-1, they delayed the poll's issue; with the
+          // io-first MFMAs: c3 12.06 -> 11.92, c2 4.95 -> 4.72 ms/step).  A/B bit 27: the old place
+          if (late_bits && tid < NC8) dbl[((s - 1) & 1) * NC8 + tid] = drop_bits(s - 1, tid);
           while (true) {
-#pragma unroll
-            for (int i = 0; i < PLN; ++i)
-              if (!partial || !tags_ok(hv[i], tag, true, true)) hv[i] = ld_sc1_b128(xr, poll_off(i) * sizeof(short));
-            // step s-1's dropout keep bits, drawn while the first poll's loads are in flight
-            // (drawn before them, at the end of step s-1, they delayed the poll's issue; with the
-            // io-first MFMAs: c3 12.06 -> 11.92, c2 4.95 -> 4.72 ms/step).  A/B bit 27: the old place
-            if (late_bits && spins == 0 && tid < NC8) dbl[((s - 1) & 1) * NC8 + tid] = drop_bits(s - 1, tid);
             bool ok = true;
 #pragma unroll
             for (int i = 0; i < PLN; ++i) ok &= tags_ok(hv[i], tag, true, true);
+            if constexpr (DBG) {
+              if (wsel) {
+#pragma unroll
+                for (int i = 0; i < (PLN < 2 ? PLN : 2); ++i)
+                  if (!wtk[1 + i] && __all(tags_ok(hv[i], tag, true, true))) wtk[1 + i] = __builtin_amdgcn_s_memtime();
+              }
+            }
             if (__all(ok)) break;
             if (++spins > SPIN_LIMIT) {
               if (lane == 0) { atomicExch(a.err, 1); abort_flag = 1; }
@@ -489,14 +508,24 @@ __global__ __launch_bounds__(W12 ? 768 : 512, W12 ? 1 : OCC) void lstm_fwd_wide_
             if (partial && (DMODE(a) & (1 << 30))) __builtin_amdgcn_s_sleep(1);
             else if (partial || (DMODE(a) & 262144)) __builtin_amdgcn_s_sleep(2);
             else __builtin_amdgcn_s_sleep(6);
+            // retry sweep: every chunk again, or (partial) only those whose tags were stale
+#pragma unroll
+            for (int i = 0; i < PLN; ++i)
+              if (!partial || !tags_ok(hv[i], tag, true, true)) hv[i] = ld_sc1_b128(xr, poll_off(i) * sizeof(short));
           }
           LSTAMP(1);
           RTS(8 + wave);
+          if constexpr (DBG) {
+            if (wsel && DPTR(a) && !(DMODE(a) & 16) && blockIdx.x == 0 && lane == 0 &&
+                (unsigned)(s - STW0) < (unsigned)STWN)
+              stamp_lds[(s - STW0) * 16 + 8 + wave] = wtk[(wsel + 2) % 3];  // (selector 1 .. 3 -> 0 .. 2)
+          }
 #pragma unroll
           for (int i = 0; i < PLN; ++i)
             *reinterpret_cast<u32x4*>(hb + (16 * (i % NT) + bi) * ROWB + swz(bi, (wave * PL + i / NT) * 4 + q) * 16) = hv[i];
         }
-        if (wave < 8) LWSTAMP();  // (stamp slots 8 .. 15)
+        // (stamp slots 8 .. 15: the wave's arrival at the barrier, unless bits 21-22 select a poll stamp)
+        if (wave < 8 && !(DBG && ((DMODE(a) >> 21) & 3))) LWSTAMP();
         __syncthreads();  // h image of step s complete; gx ring slot s & 1 landed
         LSTAMP(2);
         if (abort_flag) break;

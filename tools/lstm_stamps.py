@@ -6,6 +6,9 @@ stamps s_memtime at the kernel's STAMP(0..4) points; ticks are shader cycles).
 Phases (wide kernels; stamps of steps 64..95 buffered in LDS, lstm_common.h LSTAMP):
   fwd: 0 step start | 1 poll done | 2 barrier | 3 MFMA issued | 4 cell + publish | 6 out ring |
        7 drop bits (5: publish ack, debug bit 23)
+       per-wave line (slots 8 + wave): each polling wave's arrival at the barrier; --mode with
+       bits 21-22 = 1 / 2 / 3 (2097152 / 4194304 / 6291456): the start of the wave's first poll
+       sweep / the moment its first / second k-chunk first carries the step's tag
   bwd: 0 step start | 1 poll done | 5 cell inputs staged | 6 prefetch issued | 2 reduce done |
        7 barrier | 3 prefetch issued (late, full-chip grids) | 4 MFMA + publish
 """
@@ -98,7 +101,9 @@ def main():
         wv = [(w[:, 8 + k] - w[:, 0]).median().item() for k in range(8) if (w[:, 8 + k] != 0).all()]
     if wv:
         what = ("reduce done" if a.mode & (1 << 21) else "pre-barrier" if a.mode & (1 << 22) else "poll done")
-        print(f"per-wave {what:11s} " + " ".join(f"w{k}:{v:.0f}" for k, v in enumerate(wv)))
+        if not a.bwd:
+            what = ("at barrier", "poll start", "chunk 0 tagged", "chunk 1 tagged")[(a.mode >> 21) & 3]
+        print(f"per-wave {what:14s} " + " ".join(f"w{k}:{v:.0f}" for k, v in enumerate(wv)))
         if len(wv) == 8:
             mx = (w[:, 8:16].max(dim=1).values - w[:, 0]).median().item()
             print(f"{'':20s} slowest wave per step: median {mx:.0f}")
