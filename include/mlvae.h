@@ -1141,6 +1141,33 @@ size_t mlvae_w2v_norm_bwd_workspace_size(size_t n);
 int mlvae_w2v_norm_bwd(size_t n, const float* dy, const float* xhat, const float* stats, float* dx, void* ws,
                        size_t ws_bytes, void* stream);
 
+/* ---- The conv stack's backward (csrc/w2v.hip; DESIGN.md section 4, "The wav2vec2 encoder", "Backward",
+ * "The conv stack"): what training the feature extractor (SpeechBrain's freeze: False alone) adds.
+ * Layers >= 1 are matrix products again -- the input gradient one GEMM per residue of the frame index
+ * modulo the stride over overlapping rows of the guarded output gradient, the weight gradient dy^T times
+ * the input's windows -- so only two kernels are new.  Stream-ordered, no atomics, fixed reduction
+ * orders: a rerun is bit-identical.
+ *
+ * conv0_bwd: the backward of mlvae_w2v_conv0 (same arguments, same supported sizes) given dout
+ *   [B, T0, C] fp32, the gradient at its output: dw [C, K], dbias / dgamma / dbeta [C].  The pre-LN
+ *   activation is never stored: a wave recomputes each of its frames from the waveform, keeps its
+ *   channels' sums in registers over the consecutive frames it walks and writes one partial row of
+ *   (K + 3) C floats into ws (conv0_bwd_workspace_size bytes); a second kernel adds the rows in wave
+ *   order (fp64).  dout is read once.  There is no input gradient.  conv0_bwd_set_max_blocks: the cap on
+ *   the workgroups (default 256), returns the previous value, values < 1 only query; host-side planning
+ *   state for A/B timing -- a workspace sized before a change of the cap does not fit after it.
+ * pad_rows: x [B, T, C] fp32 -> out [B, pad_front + T + pad_back, C] as fp32 or bf16 with zero rows
+ *   before and after every utterance (C % 4 == 0, 16-byte aligned buffers): the guard rows that keep a
+ *   residue GEMM's overlapping rows inside their utterance. */
+int mlvae_w2v_conv0_bwd_set_max_blocks(int blocks);
+size_t mlvae_w2v_conv0_bwd_workspace_size(int B, int T0, int C, int K);
+int mlvae_w2v_conv0_bwd(int B, int N, int T0, int C, int K, int stride, const float* wav, const float* stats,
+                        const float* w, const float* bias, const float* gamma, const float* beta, float eps,
+                        const float* dout, float* dw, float* dbias, float* dgamma, float* dbeta, void* ws,
+                        size_t ws_bytes, void* stream);
+int mlvae_w2v_pad_rows(int B, int T, int C, int pad_front, int pad_back, const float* x, void* out, int out_bf16,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

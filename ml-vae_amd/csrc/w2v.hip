@@ -21,6 +21,10 @@
 //   attention_bwd_kernel         D = sum_k P dP, dQ (waves own queries), dK / dV (waves own keys): three
 //                                 passes of one kernel, P recomputed from the forward's log-sum-exp
 //   rows_bwd_kernel / _fold       the row kernel's backward, dgamma / dbeta from per-wave partial rows
+//   conv0_bwd_kernel / _fold      conv0_kernel's backward: dW, dbias, dgamma, dbeta, the pre-LN activation
+//                                 recomputed from the waveform, per-wave partial rows
+//   pad_rows_kernel               zero guard rows around every utterance of a conv layer's output gradient
+//                                 (the strided conv's input gradient is one GEMM per residue over them)
 //   norm_bwd_partial/_final/_apply  the whole-tensor norm's backward
 // No atomics; every reduction runs in a fixed order, so the outputs are bit-reproducible.
 #include "common.h"
@@ -756,6 +760,186 @@ __global__ __launch_bounds__(NT) void rows_bwd_fold(int nw, int C, const float* 
   else dbeta[c - C] = (float)s;
 }
 
+// ------------------------------------------------------------------ conv layer 0's backward
+// dW [C][K], dbias, dgamma, dbeta of conv0_kernel from the gradient at its output, nothing stored in
+// between: the wave recomputes a frame's window, y = conv + bias and the LN statistics exactly as the
+// forward does, goes back through GELU and LN, and keeps the CPL x K weight-gradient sums and the three
+// CPL-vectors of its channels in registers over the `per` consecutive frames it walks.  Every wave
+// writes its partial row part[wave][C K | C | C | C] (frames or not) and conv0_bwd_fold adds the rows
+// in wave order.  There is no input gradient: the waveform carries none.
+constexpr int CONV0_BWD_FRAMES = 16;  // a wave has at least this many frames before another one starts
+// a partial row is (K + 3) C floats (26 KB at C = 512, K = 10), so the fold's traffic grows with the
+// waves: DESIGN.md section 4, "The conv stack", has the caps this one was measured against
+int conv0_bwd_max_blocks = 256;
+
+int conv0_bwd_blocks(long long frames) {
+  long long waves = (frames + CONV0_BWD_FRAMES - 1) / CONV0_BWD_FRAMES;
+  long long b = (waves + NT / 64 - 1) / (NT / 64);
+  if (b < 1) b = 1;
+  if (b > conv0_bwd_max_blocks) b = conv0_bwd_max_blocks;
+  return (int)b;
+}
+
+template <int CPL>
+__global__ __launch_bounds__(NT) void conv0_bwd_kernel(int B, int N, int T0, int C, int K, int stride,
+                                                       long long per, const float* __restrict__ wav,
+                                                       const float* __restrict__ stats,
+                                                       const float* __restrict__ w,
+                                                       const float* __restrict__ bias,
+                                                       const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, float eps,
+                                                       const float* __restrict__ dout, int vec,
+                                                       float* __restrict__ part) {
+  const int lane = threadIdx.x & 63;
+  const long long wave = (long long)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+  const long long frames = (long long)B * T0;
+  const long long f0 = wave * per;
+  const long long f1 = f0 + per < frames ? f0 + per : frames;
+  float wr[CPL][CONV0_KMAX], br[CPL], gr[CPL], be[CPL];
+  float dw[CPL][CONV0_KMAX], db[CPL], dg[CPL], dbe[CPL];
+#pragma unroll
+  for (int i = 0; i < CPL; ++i) {
+    const int c = lane * CPL + i;
+    const bool ok = c < C;
+#pragma unroll
+    for (int k = 0; k < CONV0_KMAX; ++k) {
+      wr[i][k] = (ok && k < K) ? w[(size_t)c * K + k] : 0.f;
+      dw[i][k] = 0.f;
+    }
+    br[i] = ok ? bias[c] : 0.f;
+    gr[i] = ok ? gamma[c] : 0.f;
+    be[i] = ok ? beta[c] : 0.f;
+    db[i] = dg[i] = dbe[i] = 0.f;
+  }
+  const float mean = stats ? stats[0] : 0.f, rstd = stats ? stats[1] : 1.f;
+  const float invC = 1.f / (float)C;
+  // a frame's slice of dout, the one HBM stream of the kernel (channels past C: 0)
+  auto fetch = [&](long long f, float* d) {
+    const size_t o = (size_t)f * C + (size_t)lane * CPL;
+    if constexpr (CPL % 4 == 0) {
+      if (vec) {  // C % 4 == 0: a lane's quad is inside the row or wholly past it
+#pragma unroll
+        for (int j = 0; j < CPL / 4; ++j) {
+          f32x4 q = {0.f, 0.f, 0.f, 0.f};
+          if (lane * CPL + 4 * j < C) q = *reinterpret_cast<const f32x4*>(dout + o + 4 * j);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) d[4 * j + e] = q[e];
+        }
+        return;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) d[i] = lane * CPL + i < C ? dout[o + i] : 0.f;
+  };
+  float dn[CPL];
+#pragma unroll
+  for (int i = 0; i < CPL; ++i) dn[i] = 0.f;
+  if (f0 < f1) fetch(f0, dn);
+  for (long long f = f0; f < f1; ++f) {
+    const int b = (int)(f / T0), t = (int)(f - (long long)b * T0);
+    const float* xw = wav + (size_t)b * N + (size_t)t * stride;  // t stride + K <= N by T0's definition
+    // the output's gradient: this frame's was fetched a frame ago, the next one's goes out now
+    float dv[CPL];
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) dv[i] = dn[i];
+    if (f + 1 < f1) fetch(f + 1, dn);
+    // the forward again, in its order
+    float xv[CONV0_KMAX];
+#pragma unroll
+    for (int k = 0; k < CONV0_KMAX; ++k) xv[k] = k < K ? (xw[k] - mean) * rstd : 0.f;
+    float y[CPL];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+      float a = 0.f;
+#pragma unroll
+      for (int k = 0; k < CONV0_KMAX; ++k) a = fmaf(wr[i][k], xv[k], a);
+      y[i] = a + br[i];
+      if (lane * CPL + i < C) s += y[i];
+    }
+    const float mu = wave_sum(s) * invC;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+      const float d = y[i] - mu;
+      if (lane * CPL + i < C) q += d * d;
+    }
+    const float rs = 1.f / sqrtf(wave_sum(q) * invC + eps);
+    // back through GELU and LN (dv of a channel past C is 0, and so is everything it feeds)
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+      const float xh = (y[i] - mu) * rs;
+      const float dz = dv[i] * gelu_erf_grad(xh * gr[i] + be[i]);
+      dg[i] = fmaf(dz, xh, dg[i]);
+      dbe[i] += dz;
+      y[i] = xh;
+      dv[i] = dz * gr[i];
+      s1 += dv[i];
+      s2 = fmaf(dv[i], xh, s2);
+    }
+    const float m1 = wave_sum(s1) * invC, m2 = wave_sum(s2) * invC;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+      const float dy = lane * CPL + i < C ? (dv[i] - m1 - y[i] * m2) * rs : 0.f;
+      db[i] += dy;
+#pragma unroll
+      for (int k = 0; k < CONV0_KMAX; ++k) dw[i][k] = fmaf(dy, xv[k], dw[i][k]);
+    }
+  }
+  float* p = part + (size_t)wave * (size_t)C * (K + 3);
+#pragma unroll
+  for (int i = 0; i < CPL; ++i) {
+    const int c = lane * CPL + i;
+    if (c < C) {
+#pragma unroll
+      for (int k = 0; k < CONV0_KMAX; ++k)
+        if (k < K) p[(size_t)c * K + k] = dw[i][k];
+      p[(size_t)C * K + c] = db[i];
+      p[(size_t)C * (K + 1) + c] = dg[i];
+      p[(size_t)C * (K + 2) + c] = dbe[i];
+    }
+  }
+}
+
+// dW [C K] | dbias [C] | dgamma [C] | dbeta [C] = the waves' partial rows summed in wave order, one
+// thread per column (fp64: a serial fp32 chain over a thousand partials would round a thousand times)
+__global__ __launch_bounds__(NT) void conv0_bwd_fold(int nw, int C, int K, const float* __restrict__ part,
+                                                     float* __restrict__ dw, float* __restrict__ dbias,
+                                                     float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  const int ncol = C * (K + 3);
+  const int c = blockIdx.x * NT + threadIdx.x;
+  if (c >= ncol) return;
+  double s = 0.0;
+#pragma unroll 8
+  for (int wv = 0; wv < nw; ++wv) s += (double)part[(size_t)wv * ncol + c];
+  if (c < C * K) dw[c] = (float)s;
+  else if (c < C * (K + 1)) dbias[c - C * K] = (float)s;
+  else if (c < C * (K + 2)) dgamma[c - C * (K + 1)] = (float)s;
+  else dbeta[c - C * (K + 2)] = (float)s;
+}
+
+// ------------------------------------------------------------------ guard rows for the strided conv's dgrad
+// x [B, T, C] fp32 -> [B, pf + T + pa, C] (fp32 or bf16) with zero rows before and after every
+// utterance: the conv layers' output gradient as the residue GEMMs of the input gradient read it
+template <bool OUT_BF16>
+__global__ __launch_bounds__(NT) void pad_rows_kernel(int B, int T, int C, int pf, int TP,
+                                                      const float* __restrict__ x, void* __restrict__ out) {
+  const int C4 = C / 4;
+  const size_t n = (size_t)B * TP * C4;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)gridDim.x * NT) {
+    const int c4 = (int)(i % C4);
+    const size_t r = i / C4;
+    const int tp = (int)(r % TP), b = (int)(r / TP);
+    const int t = tp - pf;
+    const f32x4 v = (t >= 0 && t < T) ? reinterpret_cast<const f32x4*>(x)[((size_t)b * T + t) * C4 + c4] : zero;
+    if constexpr (OUT_BF16)
+      reinterpret_cast<bf16x4*>(out)[i] = bf16x4{f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
+    else reinterpret_cast<f32x4*>(out)[i] = v;
+  }
+}
+
 // ------------------------------------------------------------------ whole-tensor norm backward
 __global__ __launch_bounds__(NT) void norm_bwd_partial(size_t n, const float* __restrict__ dy,
                                                        const float* __restrict__ xh,
@@ -1013,6 +1197,66 @@ extern "C" int mlvae_w2v_norm_bwd(size_t n, const float* dy, const float* xhat, 
   norm_bwd_partial<<<nb, NT, 0, st>>>(n, dy, xhat, part);
   norm_bwd_final<<<1, NT, 0, st>>>(n, nb, part, means);
   norm_bwd_apply<<<stream_grid(n), NT, 0, st>>>(n, dy, xhat, stats, means, dx);
+  MLVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int mlvae_w2v_conv0_bwd_set_max_blocks(int blocks) {
+  const int prev = conv0_bwd_max_blocks;
+  if (blocks >= 1) conv0_bwd_max_blocks = blocks;
+  return prev;
+}
+
+extern "C" size_t mlvae_w2v_conv0_bwd_workspace_size(int B, int T0, int C, int K) {
+  if (B < 1 || T0 < 1 || C < 1 || K < 1) return 0;
+  return (size_t)conv0_bwd_blocks((long long)B * T0) * (NT / 64) * (size_t)C * (K + 3) * sizeof(float);
+}
+
+extern "C" int mlvae_w2v_conv0_bwd(int B, int N, int T0, int C, int K, int stride, const float* wav,
+                                   const float* stats, const float* w, const float* bias, const float* gamma,
+                                   const float* beta, float eps, const float* dout, float* dw, float* dbias,
+                                   float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream) {
+  if (!mlvae_w2v_conv0_supported(C, K) || B < 1 || stride < 1 || T0 < 1 || N < K ||
+      (long long)(T0 - 1) * stride + K > N || !wav || !w || !bias || !gamma || !beta || !dout || !dw || !dbias ||
+      !dgamma || !dbeta || !ws || ((uintptr_t)ws % 4) ||
+      ws_bytes < mlvae_w2v_conv0_bwd_workspace_size(B, T0, C, K)) {
+    mlvae_set_error("w2v_conv0_bwd: B=%d N=%d T0=%d C=%d K=%d stride=%d unsupported (C <= 512, K <= %d, "
+                    "(T0 - 1) stride + K <= N, dout and the four gradients, a workspace of %zu bytes)", B, N, T0,
+                    C, K, stride, CONV0_KMAX, mlvae_w2v_conv0_bwd_workspace_size(B, T0, C, K));
+    return 1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const long long frames = (long long)B * T0;
+  const int nb = conv0_bwd_blocks(frames), nw = nb * (NT / 64);
+  const long long per = (frames + nw - 1) / nw;
+  const int vec = C % 4 == 0 && (uintptr_t)dout % 16 == 0;
+  float* part = static_cast<float*>(ws);
+#define W2V_CONV0_BWD(CPL)                                                                                   \
+  conv0_bwd_kernel<CPL><<<nb, NT, 0, st>>>(B, N, T0, C, K, stride, per, wav, stats, w, bias, gamma, beta, eps, \
+                                           dout, vec, part)
+  if (C <= 64) W2V_CONV0_BWD(1);
+  else if (C <= 128) W2V_CONV0_BWD(2);
+  else if (C <= 256) W2V_CONV0_BWD(4);
+  else W2V_CONV0_BWD(8);
+#undef W2V_CONV0_BWD
+  conv0_bwd_fold<<<(C * (K + 3) + NT - 1) / NT, NT, 0, st>>>(nw, C, K, part, dw, dbias, dgamma, dbeta);
+  MLVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int mlvae_w2v_pad_rows(int B, int T, int C, int pad_front, int pad_back, const float* x, void* out,
+                                  int out_bf16, void* stream) {
+  if (B < 1 || T < 1 || C < 4 || C % 4 || pad_front < 0 || pad_back < 0 || !x || !out ||
+      (((uintptr_t)x | (uintptr_t)out) % 16)) {
+    mlvae_set_error("w2v_pad_rows: B=%d T=%d C=%d pads %d / %d unsupported (C %% 4 == 0, 16-byte aligned buffers)",
+                    B, T, C, pad_front, pad_back);
+    return 1;
+  }
+  const int TP = pad_front + T + pad_back;
+  const size_t n = (size_t)B * TP * (C / 4);
+  hipStream_t st = (hipStream_t)stream;
+  if (out_bf16) pad_rows_kernel<true><<<stream_grid(n), NT, 0, st>>>(B, T, C, pad_front, TP, x, out);
+  else pad_rows_kernel<false><<<stream_grid(n), NT, 0, st>>>(B, T, C, pad_front, TP, x, out);
   MLVAE_CHECK_LAUNCH();
   return 0;
 }

@@ -226,6 +226,11 @@ _SIGS = {
     "mlvae_w2v_rows_bwd": [I, I, P, P, P, P, P, F, I, P, P, P, P, P, P, SZ, P],
     "mlvae_w2v_norm_bwd_workspace_size": [SZ],
     "mlvae_w2v_norm_bwd": [SZ, P, P, P, P, P, SZ, P],
+    # the conv stack's backward
+    "mlvae_w2v_conv0_bwd_set_max_blocks": [I],
+    "mlvae_w2v_conv0_bwd_workspace_size": [I, I, I, I],
+    "mlvae_w2v_conv0_bwd": [I, I, I, I, I, I, P, P, P, P, P, P, F, P, P, P, P, P, P, SZ, P],
+    "mlvae_w2v_pad_rows": [I, I, I, I, I, P, P, I, P],
 }
 _RESTYPE = {
     "mlvae_last_error": C.c_char_p,
@@ -259,6 +264,7 @@ _RESTYPE = {
     "mlvae_w2v_stats_workspace_size": SZ,
     "mlvae_w2v_rows_bwd_workspace_size": SZ,
     "mlvae_w2v_norm_bwd_workspace_size": SZ,
+    "mlvae_w2v_conv0_bwd_workspace_size": SZ,
 }
 
 _lib = None

@@ -46,7 +46,8 @@ from .features import (  # noqa: F401
 )
 from .w2v import (  # noqa: F401
     w2v_attention, w2v_attention_bwd, w2v_attention_supported, w2v_attention_train, w2v_cast, w2v_colsum,
-    w2v_conv0, w2v_conv_gemm, w2v_gemm, w2v_linear, w2v_linear_dw, w2v_linear_dx, w2v_norm_bwd,
+    w2v_conv0, w2v_conv0_bwd, w2v_conv_dw, w2v_conv_dx, w2v_conv_dx_weights, w2v_conv_gemm, w2v_conv_pad, w2v_gemm,
+    w2v_linear, w2v_linear_dw, w2v_linear_dx, w2v_norm_bwd,
     w2v_pos_conv, w2v_pos_conv_dw, w2v_pos_conv_dx, w2v_regroup, w2v_rows, w2v_rows_bwd, w2v_scale_shift,
-    w2v_tensor_stats, W2VHeadFn, W2VLayerFn, W2VTailFn
+    w2v_tensor_stats, W2VConvFn, W2VHeadFn, W2VLayerFn, W2VTailFn
 )

@@ -329,9 +329,180 @@ def w2v_pos_conv_dw(dpc, hp, T, C):
     return out
 
 
+# ---- the conv stack's backward ("The wav2vec2 encoder", "Backward", "The conv stack")
+def w2v_conv0_bwd(wav, stats, w, bias, gamma, beta, stride, dout, eps=1e-5):
+    """The backward of w2v_conv0 given dout [B, T0, C] fp32, the gradient at its output: (dw [C, K],
+    dbias, dgamma, dbeta).  The pre-LN activation is recomputed from the waveform, never stored;
+    fixed-order sums, no input gradient (the waveform carries none, and neither do stats)."""
+    wav, dout = _w2v_dev(wav, "w2v_conv0_bwd wav"), _w2v_dev(dout, "w2v_conv0_bwd dout")
+    B, N = wav.shape
+    C, K = w.shape
+    if not lib().mlvae_w2v_conv0_supported(C, K):
+        raise ValueError(f"w2v_conv0_bwd: C = {C}, K = {K} unsupported (C <= 512, K <= 10)")
+    if N < K:
+        raise ValueError(f"w2v_conv0_bwd: {N} samples are shorter than the kernel ({K})")
+    T0 = (N - K) // stride + 1
+    if tuple(dout.shape) != (B, T0, C):
+        raise ValueError(f"w2v_conv0_bwd: dout is {tuple(dout.shape)}, expected {(B, T0, C)}")
+    for t, n in ((w, "w"), (bias, "bias"), (gamma, "gamma"), (beta, "beta")):
+        _w2v_dev(t, "w2v_conv0_bwd " + n)
+    dw = torch.empty(C, K, device=wav.device, dtype=torch.float32)
+    db, dg, dbe = (torch.empty(C, device=wav.device, dtype=torch.float32) for _ in range(3))
+    with torch.cuda.device(wav.device):
+        nbytes = lib().mlvae_w2v_conv0_bwd_workspace_size(B, T0, C, K)
+        ws = _workspace(nbytes, "w2v_conv0_bwd")
+        check(lib().mlvae_w2v_conv0_bwd(B, N, T0, C, K, stride, _p(wav), None if stats is None else _p(stats),
+                                        _p(w), _p(bias), _p(gamma), _p(beta), float(eps), _p(dout), _p(dw), _p(db),
+                                        _p(dg), _p(dbe), _p(ws), _ws_bytes(ws), _stream()), "w2v_conv0_bwd")
+    return dw, db, dg, dbe
+
+
+def _conv_geometry(k, stride, T_in):
+    """(Tout, taps per residue m_r, guard rows before, guard rows after) of a strided conv's input
+    gradient.  Input frame n = stride u + r takes dx[n] = sum_{q < m_r} dy[u - q] W[:, :, r + q stride],
+    m_r = ceil((k - r) / stride), dy = 0 outside [0, Tout): u - q reaches m_0 - 1 rows before the first
+    frame and u reaches ceil(T_in / stride) - 1, at or past the last."""
+    if not 1 <= stride <= k:
+        raise ValueError(f"w2v_conv_dx: stride {stride} against kernel {k} is unsupported (1 <= stride <= k)")
+    if T_in < k:
+        raise ValueError(f"w2v_conv_dx: {T_in} frames are shorter than the kernel ({k})")
+    Tout = (T_in - k) // stride + 1
+    m = [-((r - k) // stride) for r in range(stride)]
+    return Tout, m, m[0] - 1, -(-T_in // stride) - Tout
+
+
+def w2v_conv_dx_weights(w, stride, dtype):
+    """The conv weight [Cout, Cin, k] regrouped for w2v_conv_dx: per residue r the taps r, r + stride,
+    ... in reverse order with in / out swapped, [Cin, m_r Cout] in `dtype`."""
+    Cout, Cin, k = w.shape
+    _, m, _, _ = _conv_geometry(k, stride, k)
+    return [w[:, :, r::stride].flip(-1).permute(1, 2, 0).reshape(Cin, m[r] * Cout).to(dtype).contiguous()
+            for r in range(stride)]
+
+
+def w2v_conv_pad(dy, k, stride, T_in, dtype):
+    """dy [B, Tout, Cout] fp32 with the zero guard rows of w2v_conv_dx before and after every
+    utterance, in `dtype` (fp32 or bf16): ([B, pf + Tout + pa, Cout], pf).  One kernel: the copy is the
+    bf16 mode's operand cast as well, and w2v_conv_dw reads the same copy."""
+    dy = _w2v_dev(dy, "w2v_conv_pad dy")
+    B, Tout, Cout = dy.shape
+    T, _, pf, pa = _conv_geometry(k, stride, T_in)
+    if T != Tout:
+        raise ValueError(f"w2v_conv_pad: dy has {Tout} frames, a conv of {T_in} frames gives {T}")
+    if pf == 0 and pa == 0 and dtype == torch.float32:
+        return dy, 0
+    out = torch.empty(B, pf + Tout + pa, Cout, device=dy.device, dtype=dtype)
+    with torch.cuda.device(dy.device):
+        check(lib().mlvae_w2v_pad_rows(B, Tout, Cout, pf, pa, _p(dy), out.data_ptr(),
+                                       int(dtype == torch.bfloat16), _stream()), "w2v_pad_rows")
+    return out, pf
+
+
+def w2v_conv_dx(dy, W, k, stride, T_in, padded=None):
+    """The strided conv's input gradient dx [B, T_in, Cin] fp32 from dy [B, Tout, Cout] fp32: one GEMM
+    per residue r over overlapping rows of the guarded dy (lda = Cout, m_r Cout wide), written at
+    ldc = stride Cin with column offset r Cin -- the exact dgrad's FLOPs, no zero blocks and no
+    column tensor.  W: w2v_conv_dx_weights (their dtype is the operand dtype); padded: w2v_conv_pad's
+    result when the caller already has it.  Frames at or past (Tout - 1) stride + k get exactly 0."""
+    Tout, m, pf, pa = _conv_geometry(k, stride, T_in)
+    if len(W) != stride:
+        raise ValueError(f"w2v_conv_dx: {len(W)} residue weights for stride {stride}")
+    dyp, pf_ = padded if padded is not None else w2v_conv_pad(dy, k, stride, T_in, W[0].dtype)
+    B, TP, Cout = dyp.shape
+    Cin = W[0].shape[0]
+    if TP != pf + Tout + pa or pf_ != pf or dyp.dtype != W[0].dtype or any(
+            tuple(W[r].shape) != (Cin, m[r] * Cout) for r in range(stride)):
+        raise ValueError(f"w2v_conv_dx: dy {tuple(dyp.shape)} / weights {[tuple(t.shape) for t in W]} do not fit "
+                         f"k = {k}, stride = {stride}, T_in = {T_in}")
+    dx = torch.empty(B, T_in, Cin, device=dyp.device, dtype=torch.float32)
+    flat, out = dyp.view(-1), dx.view(-1)
+    for r in range(stride):
+        U = -(-(T_in - r) // stride)  # the frames of this residue
+        w2v_gemm(flat[(pf - (m[r] - 1)) * Cout:], W[r], out[r * Cin:], U, Cin, m[r] * Cout, Cout, stride * Cin,
+                 batch=B, a_bs=TP * Cout, c_bs=T_in * Cin)
+    return dx
+
+
+def w2v_conv_dw(dy, x, k, stride):
+    """The conv weight's gradient [Cout, k Cin] fp32 (the kernel-side [Cout][k][Cin] order): per
+    utterance dy_b^T [Cout, Tout] times the overlapping-row windows of x_b [B, T_in, Cin] on the B
+    side (ldb = stride Cin), the utterances summed in order (beta = 1 from the second on).  dy
+    [B, Tout, Cout] in x's dtype; its utterances may lie apart (a slice of the guarded copy)."""
+    B, Tout, Cout = dy.shape
+    _, T_in, Cin = x.shape
+    if Tout != (T_in - k) // stride + 1 or dy.dtype != x.dtype or dy.stride()[1:] != (Cout, 1):
+        raise ValueError(f"w2v_conv_dw: dy {tuple(dy.shape)} ({dy.dtype}) against x {tuple(x.shape)} ({x.dtype}), "
+                         f"k = {k}, stride = {stride}")
+    out = torch.empty(Cout, k * Cin, device=x.device, dtype=torch.float32)
+    for b in range(B):
+        w2v_gemm(dy[b], x[b], out, Cout, k * Cin, Tout, Cout, k * Cin, beta=0.0 if b == 0 else 1.0, ta=1, tb=0,
+                 ldb=stride * Cin)
+    return out
+
+
+class W2VConvFn(torch.autograd.Function):
+    """normalize_wav and the conv layers on wav [B, N]: the last layer's fp32 output [B, T, conv_dim]
+    (Wav2Vec2._conv_stack's kernel sequence unchanged: the same bits).  P: the kernel-side weights; geo:
+    (kernels, strides, eps, bf, normalize_wav, stages).  The trailing tensors are the fp32 masters the
+    gradients go to, four per layer: conv weight / bias, LN weight / bias.  Saved: the waveform and its
+    statistics (layer 0 is recomputed in its backward), and per layer i >= 1 its input in the GEMM
+    operand dtype (what the forward produces anyway) and its fp32 pre-LN output."""
+
+    @staticmethod
+    def forward(ctx, wav, P, geo, *masters):
+        ks, ss, eps, bf, normalize_wav, stages = geo
+        ad = torch.bfloat16 if bf else torch.float32
+        keep = (lambda n, t: stages.__setitem__(n, t.float().clone())) if stages is not None else (lambda n, t: None)
+        wav = wav.detach().float().contiguous()
+        stats = w2v_tensor_stats(wav) if normalize_wav else None
+        W, b, g, be = P["conv"][0][:4]
+        x = w2v_conv0(wav, stats, W, b, g, be, ss[0], eps, out_dtype=ad)
+        keep("conv0", x)
+        n_conv = len(ks)
+        xf = x if not bf else None
+        saved = [wav, stats]
+        for i in range(1, n_conv):
+            W, b, g, be = P["conv"][i][:4]
+            y = w2v_conv_gemm(x, W, b, ks[i], ss[i])
+            last = i == n_conv - 1
+            saved += [x, y]
+            xf, xb = w2v_rows(y, gamma=g, beta=be, eps=eps, gelu=True, out_f32=last or not bf,
+                              out_bf16=bf and not last)
+            x = xb if xb is not None else xf
+            keep(f"conv{i}", x)
+        if xf is None:  # a one-layer conv stack in bf16: conv0 wrote bf16
+            xf = x.float()
+        ctx.save_for_backward(*saved)
+        ctx.P, ctx.geo = P, geo
+        return xf
+
+    @staticmethod
+    def backward(ctx, d):
+        wav, stats, *acts = ctx.saved_tensors
+        P, (ks, ss, eps, bf, _, _) = ctx.P, ctx.geo
+        ad = torch.bfloat16 if bf else torch.float32
+        d = d.contiguous()
+        grads = []
+        for i in range(len(ks) - 1, 0, -1):
+            x, y = acts[2 * (i - 1)], acts[2 * (i - 1) + 1]
+            W, _, g, be, Wdx = P["conv"][i]
+            B, T_in, Cin = x.shape
+            Cout = y.shape[2]
+            dy, _, d_g, d_be = w2v_rows_bwd(d, y, gamma=g, beta=be, eps=eps, gelu=True, out_f32=True)
+            d_b = w2v_colsum(dy.view(-1, Cout))
+            dyp, pf = w2v_conv_pad(dy, ks[i], ss[i], T_in, ad)
+            d_w = w2v_conv_dw(dyp[:, pf:pf + dy.shape[1]], x, ks[i], ss[i])
+            d = w2v_conv_dx(None, Wdx, ks[i], ss[i], T_in, padded=(dyp, pf))
+            grads = [d_w.view(Cout, ks[i], Cin).permute(0, 2, 1).contiguous(), d_b, d_g, d_be] + grads
+        W, b, g, be = P["conv"][0][:4]
+        d_w, d_b, d_g, d_be = w2v_conv0_bwd(wav, stats, W, b, g, be, ss[0], d, eps)
+        return (None, None, None, d_w.view(W.shape[0], 1, W.shape[1]), d_b, d_g, d_be, *grads)
+
+
 class W2VHeadFn(torch.autograd.Function):
-    """The projection's LayerNorm and Linear and h += GELU(pos_conv(h) + bias) on the frozen conv
-    stack's fp32 output xf [B, T, Cc].  P: the kernel-side weights (modules/wav2vec2.py).  The
+    """The projection's LayerNorm and Linear and h += GELU(pos_conv(h) + bias) on the conv stack's
+    fp32 output xf [B, T, Cc] (frozen, or W2VConvFn's: then its gradient is returned too).  P: the
+    kernel-side weights (modules/wav2vec2.py).  The
     trailing tensors are the fp32 masters the gradients go to: LN weight / bias, projection weight /
     bias, the positional conv's bias, g, v.  Saved: xf, the LN output and the regrouped projection
     (the weight gradients' operands, bf16 in bf16 mode) and the fp32 conv output before its GELU."""
@@ -376,9 +547,11 @@ class W2VHeadFn(torch.autograd.Function):
         dhpb = w2v_cast(dhp, ad)
         d_pw = w2v_linear_dw(dhpb, x0)
         dx0 = w2v_linear_dx(dhpb, P["proj"][0])
-        _, _, d_lw, d_lb = w2v_rows_bwd(dx0, xf.view(B * T, -1), gamma=P["proj_ln"][0], beta=P["proj_ln"][1],
-                                        eps=eps, out_f32=True)  # the conv stack is frozen: dx is not used
-        return None, None, None, d_lw, d_lb, d_pw, d_pb, d_cb, d_cg, d_cv
+        dxf, _, d_lw, d_lb = w2v_rows_bwd(dx0, xf.view(B * T, -1), gamma=P["proj_ln"][0], beta=P["proj_ln"][1],
+                                          eps=eps, out_f32=True)
+        # the conv stack's gradient, when it trains (W2VConvFn); frozen: dx is not used
+        dxf = dxf.view(xf.shape) if ctx.needs_input_grad[0] else None
+        return dxf, None, None, d_lw, d_lb, d_pw, d_pb, d_cb, d_cg, d_cv
 
 
 class W2VLayerFn(torch.autograd.Function):

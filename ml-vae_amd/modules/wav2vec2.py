@@ -37,7 +37,12 @@ kernels in the same order, so the output's bits equal the frozen module's) and t
 ``parameters()`` then yields the fp32 masters of everything from ``feature_projection`` upward
 (``masked_spec_embed`` is unused without masking and stays a frozen tensor); the kernel-side copies
 are rebuilt per tensor group when a master's version counter moved (an optimizer step, a load).
-``freeze=False`` without ``freeze_feature_extractor`` raises: the conv stack has no backward.
+``freeze=False`` alone still raises as it always did (the wording is pinned); the whole model --
+what SpeechBrain 0.5.x trains under ``freeze: False`` -- is ``freeze=False, train_feature_extractor=True``:
+steps 1-2 then run through ``ops.W2VConvFn`` (the same kernels again, the same bits) and its HIP backward
+(layer 0 fused and recomputed from the waveform, layers 1.. as residue GEMMs; DESIGN.md section 4, "The
+conv stack"), and ``parameters()`` yields every tensor but ``masked_spec_embed``, the
+``feature_extractor.conv_layers.*`` ones first, in HuggingFace's order.
 Train-mode regularisation (the dropouts, layerdrop, SpecAugment masking) is not built: non-zero
 values in a config are ignored with one logged warning, and ``train()`` / ``eval()`` compute the same.
 
@@ -158,13 +163,17 @@ def _read_state(source):
 
 class Wav2Vec2(nn.Module):
     def __init__(self, source=None, config="large_lv60", output_norm=True, freeze=True, normalize_wav=True,
-                 precision="bf16", save_path=None, freeze_feature_extractor=False):
+                 precision="bf16", save_path=None, freeze_feature_extractor=False, train_feature_extractor=False):
         super().__init__()
         del save_path  # SpeechBrain's download cache: nothing is downloaded here
-        if not freeze and not freeze_feature_extractor:
+        if train_feature_extractor and (freeze or freeze_feature_extractor):
+            raise ValueError("Wav2Vec2: train_feature_extractor=True contradicts freeze=True / "
+                             "freeze_feature_extractor=True")
+        if not freeze and not freeze_feature_extractor and not train_feature_extractor:
             raise NotImplementedError("Wav2Vec2: freeze=False with freeze_feature_extractor=False is not built: "
                                       "the convolutional feature extractor has no backward; pass "
-                                      "freeze_feature_extractor=True to fine-tune everything above it")
+                                      "freeze_feature_extractor=True to fine-tune everything above it.  The "
+                                      "whole model trains with train_feature_extractor=True")
         if precision not in ("bf16", "fp32"):
             raise ValueError(f"Wav2Vec2: precision must be 'bf16' or 'fp32', got {precision!r}")
         state = None
@@ -180,6 +189,7 @@ class Wav2Vec2(nn.Module):
         self.config = resolve_config(config)
         self.output_norm, self.normalize_wav, self.precision = bool(output_norm), bool(normalize_wav), precision
         self.freeze, self.freeze_feature_extractor = bool(freeze), bool(freeze_feature_extractor)
+        self.train_feature_extractor = bool(train_feature_extractor)
         # the weights under HuggingFace's names (fp32).  Frozen: plain tensors.  Fine-tuning: the trainable
         # ones are nn.Parameters, registered under the same names
         self._w = OrderedDict()
@@ -198,14 +208,15 @@ class Wav2Vec2(nn.Module):
 
     @staticmethod
     def trainable_key(key):
-        """Whether fine-tuning trains this state-dict key: everything from the projection upward."""
+        """Whether fine-tuning above a frozen conv stack trains this state-dict key: everything from
+        the projection upward (train_feature_extractor adds the feature_extractor.* keys)."""
         return key.startswith(("feature_projection.", "encoder."))
 
     def _make_trainable(self):
         if self.freeze:
             return
         for key, shape in state_shapes(self.config).items():
-            if self.trainable_key(key):
+            if self.trainable_key(key) or (self.train_feature_extractor and key.startswith("feature_extractor.")):
                 t = self._w[key] if key in self._w else torch.zeros(shape)
                 # HuggingFace's dotted names: what register_parameter refuses and state_dict needs
                 self._parameters[key] = self._w[key] = nn.Parameter(t)
@@ -306,6 +317,9 @@ class Wav2Vec2(nn.Module):
             p = f"feature_extractor.conv_layers.{i}."
             conv = (lambda cw, cb, g, be: (cw[:, 0, :].contiguous(), cb, g, be)) if i == 0 else (
                 lambda cw, cb, g, be: (m(cw.permute(0, 2, 1).reshape(cw.shape[0], -1)), cb, g, be))  # [Cout][K][Cin]
+            if i > 0 and self.train_feature_extractor:  # with the input gradient's weights: taps regrouped by residue
+                conv = (lambda fwd, s: lambda cw, cb, g, be: fwd(cw, cb, g, be) + (
+                    ops.w2v_conv_dx_weights(cw, s, wd),))(conv, cfg["conv_stride"][i])
             out[f"conv{i}"] = ((p + "conv.weight", p + "conv.bias", p + "layer_norm.weight", p + "layer_norm.bias"),
                                conv)
         out["proj_ln"] = ln("feature_projection.layer_norm")
@@ -378,13 +392,13 @@ class Wav2Vec2(nn.Module):
 
         wav = wav.detach().float().contiguous()
         stats = ops.w2v_tensor_stats(wav) if self.normalize_wav else None
-        W, b, g, be = P["conv"][0]
+        W, b, g, be = P["conv"][0][:4]
         x = ops.w2v_conv0(wav, stats, W, b, g, be, cfg["conv_stride"][0], eps, out_dtype=ad)
         keep("conv0", x)
         n_conv = len(cfg["conv_dim"])
         xf = x if not bf else None  # the last conv layer's fp32 output feeds the projection's LN
         for i in range(1, n_conv):
-            W, b, g, be = P["conv"][i]
+            W, b, g, be = P["conv"][i][:4]
             y = ops.w2v_conv_gemm(x, W, b, cfg["conv_kernel"][i], cfg["conv_stride"][i])
             last = i == n_conv - 1
             xf, xb = ops.w2v_rows(y, gamma=g, beta=be, eps=eps, gelu=True, out_f32=last or not bf,
@@ -449,6 +463,12 @@ class Wav2Vec2(nn.Module):
             self._prep = self._prepare(wav.device)
         elif not self.freeze:  # an optimizer step since: the changed tensors' copies only
             self._prepare(wav.device, self._prep)
+        if self.train_feature_extractor:
+            geo = (cfg["conv_kernel"], cfg["conv_stride"], cfg["layer_norm_eps"], self.precision == "bf16",
+                   self.normalize_wav, stages)
+            masters = [self._w[f"feature_extractor.conv_layers.{i}.{n}"] for i in range(len(cfg["conv_dim"]))
+                       for n in ("conv.weight", "conv.bias", "layer_norm.weight", "layer_norm.bias")]
+            return self._trainable_tail(ops.W2VConvFn.apply(wav, self._prep, geo, *masters), stages)
         if not self.freeze:
             with torch.no_grad():
                 xf = self._conv_stack(wav, stages)
