@@ -621,11 +621,14 @@ int mlvae_heads_fused_ex3(int B, int T, int F, int C, int H2, int loss_type, int
 int mlvae_bf16_split_rows(const float* src, int rows, int cols, int chunk, void* dst, void* stream);
 /* Skinny products of the bottom LSTM layer (bf16; one side is the latent width):
  * mlvae_skinny_nt: C [M, N] (fp32, ldc) = A [M, K] . Bt [N, K]^T, bf16 k-contiguous operands,
- *   N in {16, 32, 48, 64}, K % 32 == 0: dZ = dG W_ih over the k-contiguous W_ih^T copy.
+ *   N in {16, 32, 48, 64}, K % 32 == 0: dZ = dG W_ih over the k-contiguous W_ih^T copy.  K == 0
+ *   reads neither operand and stores C = 0; K < 0 is refused.
  * mlvae_skinny_tn: W [M, nw] (fp32 row-major) = A^T B over K frames, A stored [K, M] (lda), B
  *   stored [K, NB] (ldb), NB in {16..64} % 16, M % 64 == 0; bias1/bias2 [M] (either may be NULL)
- *   = column nw of the product (B's column nw all ones: the bias gradient as MFMA work).  Frame
- *   splits go to fp32 slabs (workspace: mlvae_skinny_tn_workspace_size) summed in a fixed order.
+ *   = column nw of the product (B's column nw all ones: the bias gradient as MFMA work).  B's
+ *   columns beyond nw (beyond nw + 1 with a bias) are read but reach no output: they may hold
+ *   any finite values.  Frame splits go to fp32 slabs (workspace:
+ *   mlvae_skinny_tn_workspace_size) summed in a fixed order.
  * Replace the autograd of layer 0's input projection (ref:src/modules/decoder.py:14-15,22). */
 /* C[M, N] = A[M, K] B[N, K]^T + bias1 + bias2 (bf16 operands, k-contiguous, fp32 C), K in
  * {8, 16, 24, 32}, N % 16 == 0, 16-byte aligned rows; biases may be NULL.  The layer-0 LSTM
@@ -643,7 +646,8 @@ int mlvae_skinny_tn(int M, int NB, int K, const void* A, int lda, const void* B,
                     float* W, float* bias1, float* bias2, float* ws, size_t ws_bytes, void* stream);
 /* fp8 mode (configs[4]), layer 0: the same two products on the e4m3 dG the fp8 BPTT writes (lda in
  * bytes, % 16) -- converted to bf16 in registers (exact), results times *alpha (1 / dG's scale).
- * mlvae_skinny_nt_fp8 needs K % 256 and M >= 4096; mlvae_skinny_tn_fp8 mlvae_skinny_tn's workspace. */
+ * mlvae_skinny_nt_fp8 needs K > 0, K % 256 == 0 and M >= 4096 (K <= 0 is refused);
+ * mlvae_skinny_tn_fp8 mlvae_skinny_tn's workspace. */
 int mlvae_skinny_nt_fp8(int M, int N, int K, const void* A8, int lda, const void* Bt, int ldb, float* C, int ldc,
                         const float* alpha, void* stream);
 int mlvae_skinny_tn_fp8(int M, int NB, int K, const void* A8, int lda, const void* B, int ldb, int nw, float* W,

@@ -529,16 +529,18 @@ int tn_splits(int M, int K) {
 extern "C" int mlvae_skinny_nt(int M, int N, int K, const void* A, int lda, const void* Bt, int ldb,
                                float* C, int ldc, void* stream) {
   if (M <= 0) return 0;
-  if (!A || !Bt || !C || N % 16 || N < 16 || N > 64 || K % 32 || lda % 8 || ldb % 8 || ldc % 4 ||
+  if (!A || !Bt || !C || N % 16 || N < 16 || N > 64 || K < 0 || K % 32 || lda % 8 || ldb % 8 || ldc % 4 ||
       ((uintptr_t)A % 16) || ((uintptr_t)Bt % 16) || ((uintptr_t)C % 16)) {
-    mlvae_set_error("mlvae_skinny_nt: N in {16..64} %% 16, K %% 32, aligned 16-byte rows");
+    mlvae_set_error("mlvae_skinny_nt: N in {16..64} %% 16, K >= 0 and %% 32, aligned 16-byte rows");
     return 1;
   }
   const unsigned short* a = static_cast<const unsigned short*>(A);
   const unsigned short* b = static_cast<const unsigned short*>(Bt);
   hipStream_t st = (hipStream_t)stream;
-  if (K % NTL_KC == 0 && M >= 4096) {  // row streams of >= 32 workgroups: Bt shared through LDS
-                                         // (c3 409 -> 210 us, c2 52 -> 49 us)
+  // row streams of >= 32 workgroups: Bt shared through LDS (c3 409 -> 210 us, c2 52 -> 49 us).
+  // K > 0: the LDS form loads its first chunk unconditionally; K == 0 goes to the ks form, which
+  // reads nothing and stores zeros
+  if (K > 0 && K % NTL_KC == 0 && M >= 4096) {
     dim3 g128((M + 127) / 128);
     switch (N / 16) {
       case 1: skinny_nt_lds_kernel<1><<<g128, 512, 0, st>>>(M, K, a, lda, b, ldb, C, ldc, nullptr); break;
@@ -576,9 +578,9 @@ extern "C" int mlvae_skinny_nt(int M, int N, int K, const void* A, int lda, cons
 extern "C" int mlvae_skinny_nt_fp8(int M, int N, int K, const void* A8, int lda, const void* Bt, int ldb,
                                    float* C, int ldc, const float* alpha, void* stream) {
   if (M <= 0) return 0;
-  if (!A8 || !Bt || !C || !alpha || N % 16 || N < 16 || N > 64 || K % NTL_KC || M < 4096 || lda % 16 ||
+  if (!A8 || !Bt || !C || !alpha || N % 16 || N < 16 || N > 64 || K <= 0 || K % NTL_KC || M < 4096 || lda % 16 ||
       ldb % 8 || ldc % 4 || ((uintptr_t)A8 % 16) || ((uintptr_t)Bt % 16) || ((uintptr_t)C % 16)) {
-    mlvae_set_error("mlvae_skinny_nt_fp8: N in {16..64} %% 16, K %% 256, M >= 4096, aligned rows (lda %% 16 B)");
+    mlvae_set_error("mlvae_skinny_nt_fp8: N in {16..64} %% 16, K > 0 and %% 256, M >= 4096, aligned rows (lda %% 16 B)");
     return 1;
   }
   const unsigned short* b = static_cast<const unsigned short*>(Bt);
